@@ -12,8 +12,14 @@ across ranks by combination index (strong scaling: total work per step is
 fixed); each rank drives one MI355X through the native gfx950 kernels and
 ranks synchronize with torch.distributed (RCCL over xGMI).
 
+A plain run does only what the headline figure needs: set up, warm up,
+time the steps, optionally write the last step's outputs (--dump-outputs)
+and print the result line. --full additionally runs the live AES bit-0 LUT
+search that fills in final_gate_count / gate_search_seconds.
+
 Run (single GPU):   python bench.py --steps 5 --warmup 2
 Run (N GPUs):       torchrun --nproc-per-node N bench.py --gpus N ...
+Full report:        python bench.py --steps 5 --warmup 2 --full
 """
 
 import argparse
@@ -38,10 +44,20 @@ def main():
     ap.add_argument("--allow-cpu", action="store_true",
                     help="permit the CPU scan path (dev only; GPU runs must "
                          "use the gfx950 kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: "
+                         "the post-timing AES bit-0 LUT search that produces "
+                         "the final-gate-count half of the metric")
     ap.add_argument("--no-gate-search", action="store_true",
-                    help="skip the post-timing AES bit-0 LUT search that "
-                         "produces the final-gate-count half of the metric")
+                    help="with --full, skip the post-timing AES bit-0 LUT "
+                         "search")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned (found, res, evaluated) as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -89,10 +105,13 @@ def main():
     begin = total * rank // world
     end = total * (rank + 1) // world
 
+    last = {}
+
     def one_step(step_idx):
         found, res, evaluated = engine.scan_pool(
             5, st, target, mask, begin, end, seed=SCAN_SEED + step_idx,
             count_all=True)
+        last["out"] = (found, res, evaluated)
         return evaluated
 
     def sync():
@@ -132,16 +151,29 @@ def main():
         elapsed_max = elapsed
         evaluated_sum = evaluated
 
+    if args.dump_outputs and rank == 0:
+        # What a caller of the timed path received in the last timed step
+        # (this rank's slice). float64 holds every value exactly: res entries
+        # are 16-bit, evaluated <= C(pool, 5) < 2^53.
+        import numpy as np
+        found, res, last_evaluated = last["out"]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, val in (("found", [float(bool(found))]),
+                          ("res", [float(v) for v in res]),
+                          ("evaluated", [float(last_evaluated)])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                    np.asarray(val, dtype=np.float64))
+
     # The BASELINE metric is "LUT-candidates/sec + final gate count": rank 0
     # additionally runs the actual flagship search (AES S-box bit 0, 3-LUT
     # graph) end-to-end, outside the timed scan region, and reports the gate
     # count of the circuit it produced this run (validated by DAG evaluation
-    # inside find_circuit). Reference quality bar: the reference's
-    # illustrative single-output AES LUT artifact is 67 gates
-    # (/root/reference/README.md:107-112).
+    # inside find_circuit). Only with --full: a plain run reports null for
+    # both fields. Reference quality bar: the reference's illustrative
+    # single-output AES LUT artifact is 67 gates.
     final_gate_count = None
     gate_search_seconds = None
-    if rank == 0 and not args.no_gate_search and use_gpu:
+    if rank == 0 and args.full and not args.no_gate_search and use_gpu:
         from sboxgates_amd.search import find_circuit
         ts = time.perf_counter()
         best = find_circuit("rijndael", bit=0, lut=True, seed=11, gpu="force")

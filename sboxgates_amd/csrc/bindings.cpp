@@ -449,7 +449,7 @@ PYBIND11_MODULE(_core, m) {
       })
       .def("scan_pool", [](Engine& e, int k, const state& st, py::bytes target,
                            py::bytes mask, i64 begin, i64 end, u64 seed,
-                           bool count_all) {
+                           bool count_all, u64 excl) {
         std::vector<ttable> pool(st.num_gates);
         for (int i = 0; i < st.num_gates; i++) pool[i] = st.gates[i].table;
         ScanRequest rq;
@@ -457,7 +457,7 @@ PYBIND11_MODULE(_core, m) {
         rq.n = st.num_gates;
         rq.target = tt_from_bytes(target);
         rq.mask = tt_from_bytes(mask);
-        rq.excl_low64 = 0;
+        rq.excl_low64 = excl;
         rq.seed = seed;
         rq.count_all = count_all;
         if (k == 4) rq.matcher = e.matcher3();
@@ -466,5 +466,5 @@ PYBIND11_MODULE(_core, m) {
         return py::make_tuple(r.found, res, r.evaluated);
       }, py::arg("k"), py::arg("state"), py::arg("target"), py::arg("mask"),
          py::arg("begin"), py::arg("end"), py::arg("seed") = 0,
-         py::arg("count_all") = false);
+         py::arg("count_all") = false, py::arg("excl") = 0);
 }

@@ -145,7 +145,7 @@ __device__ __forceinline__ void dev_decode_triple(i64 q, int m, int* d, int* e,
 }
 
 __device__ __forceinline__ u64 dev_rnd(u64 seed, u64 idx) {
-  return hash_mix64(seed ^ (idx * 0x9E3779B97F4A7C15ULL));
+  return scan_rnd(seed, idx);
 }
 
 // Global-address-space pointer casts for cross-workgroup / host-visible
@@ -393,10 +393,35 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4(ScanArgs args) {
 // ---------------------------------------------------------------------------
 // K3 — 5-LUT scan. Workgroups dequeue triple prefixes; the 8 prefix cells
 // (masked with target-1/target-0) are computed cooperatively into LDS; each
-// thread then screens (d, e) pairs with a per-u early exit and runs the
+// thread then takes row segments — one d, a few consecutive e — hoists the
+// d side of the most balanced live cell, screens the e's against it,
+// sends what passes through the remaining live cells, and runs the
 // 2-coloring decomposition solver on survivors (replacing the reference's
 // 10 x 256-function brute force, lut.c:174-246).
 // ---------------------------------------------------------------------------
+
+// (a & b) | acc in one VALU instruction. Written out because the compiler
+// rebalances a plain C chain of these into v_and_b32 pairs feeding
+// v_or3_b32 (11 instructions per 8-dword reduction instead of 8) and keeps
+// vectorized copies of the loop-invariant operands.
+__device__ __forceinline__ u32 dev_and_or(u32 a, u32 b, u32 acc) {
+  u32 r;
+  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc));
+  return r;
+}
+
+// (a & ~b) | acc, likewise one instruction (gfx950's three-input bit op,
+// truth table 0xba), so ~te is never materialised.
+__device__ __forceinline__ u32 dev_andn_or(u32 a, u32 b, u32 acc) {
+  u32 r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba"
+      : "=v"(r) : "v"(a), "v"(b), "v"(acc));
+  return r;
+}
+
+// 16-byte LDS read of a pool row half (rows are u64 words at a 16 B
+// aligned stride; may_alias makes the differently-typed read well defined).
+typedef u32 lds_u32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
 
 // Survivor handling for k_scan5 (rare path; noinline keeps its registers
 // out of the hot loop's budget).
@@ -433,15 +458,24 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   // barrier per TB triples (measured at TB=1: 48% of wave time parked on
   // the per-triple barriers; batching amortizes them 8x).
   constexpr int TB = 8;
-  __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
+  // The row screen reads whole segments of up to SEG_MAX pool rows without
+  // per-pair bounds tests; the pad rows keep a segment that starts at the
+  // pool's last gate inside the array (their content is masked out).
+  constexpr int SEG_MAX = 16;
+  __shared__ alignas(16) u64 s_pool[(MAX_GATES + SEG_MAX) * PSTR];
   __shared__ alignas(16) u64 s_H1[TB][8][4];
   __shared__ alignas(16) u64 s_H0[TB][8][4];
   __shared__ i64 s_base[TB];     // flat-rank base of each triple
   __shared__ i64 s_lo[TB], s_prefix[TB + 1];
+  __shared__ int s_hi[TB];       // window end (flat pair index) per triple
+  __shared__ int s_tpre[TB + 1]; // prefix sums of row-segment task counts
+  __shared__ int s_seg;          // segment length of this batch
   __shared__ int s_m[TB], s_c[TB];
   __shared__ u16 s_abc[TB][3];
   __shared__ u32 s_live[TB];     // cells with both forced-1 and forced-0
                                  // content; only these can contradict
+  __shared__ u32 s_best[TB];     // (min side popcount << 3 | 7 - u) of the
+                                 // most balanced live cell: the screen cell
   __shared__ int s_stop;         // all triples past range end
   __shared__ unsigned long long s_eval;
 
@@ -499,6 +533,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       }
       s_base[t] = base;
       s_lo[t] = lo;
+      s_hi[t] = static_cast<int>(hi);  // <= C(m, 2) < 2^17
       s_m[t] = m;
       s_c[t] = c;
       s_abc[t][0] = static_cast<u16>(a);
@@ -514,6 +549,33 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       // is past the range end (or past the triple space), every later
       // batch is too.
       s_stop = (batch_base >= total3 || s_base[0] >= args.end) ? 1 : 0;
+      // Row-segment tasks. A task is (triple, row d2, segment): the pairs
+      // (d2, e2) with gap e2 - d2 - 1 in [s0, s0 + L). Segment s0 exists for
+      // the rows d2 < m - 1 - s0, so a triple has sum_s (m - 1 - s * L)
+      // tasks. L follows the batch's longest row. Long rows get SEG_MAX:
+      // measured at pool 450, 16-pair segments beat 32-pair ones by 2.6%
+      // (half the ragged-tail waste for twice the d-side hoists). Short
+      // rows (the search's small pools) get 4 pairs, the flat walk's old
+      // run length: those scans are dominated by survivors going through
+      // the solver one after another in their lane, and 8-pair segments
+      // made the AES bit-0 search 15% slower than 4-pair ones.
+      int mmax = 0;
+      for (int t = 0; t < TB; t++) {
+        if (s_prefix[t + 1] != 0 && s_m[t] > mmax) mmax = s_m[t];
+      }
+      const int lg = mmax > 40 ? 4 : 2;
+      const int L = 1 << lg;  // SEG_MAX at most
+      s_seg = L;
+      s_tpre[0] = 0;
+      for (int t = 0; t < TB; t++) {
+        int cnt = 0;
+        if (s_prefix[t + 1] != 0) {
+          const int rows = s_m[t] - 1;
+          const int ns = (rows + L - 1) >> lg;
+          cnt = ns * rows - L * (ns * (ns - 1) / 2);
+        }
+        s_tpre[t + 1] = s_tpre[t] + cnt;
+      }
       for (int t = 0; t < TB; t++) s_prefix[t + 1] += s_prefix[t];
     }
     __syncthreads();
@@ -544,7 +606,10 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
         }
       }
     }
-    if (threadIdx.x < TB) s_live[threadIdx.x] = 0;
+    if (threadIdx.x < TB) {
+      s_live[threadIdx.x] = 0;
+      s_best[threadIdx.x] = 0;
+    }
     __syncthreads();
     // Liveness: a cell whose H1 or H0 side is empty can never contradict
     // (and survivors rebuild exact p-masks anyway). Sparse-mask scans in
@@ -554,99 +619,186 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       const int u = threadIdx.x & 7;
       const u64 h1 = s_H1[t][u][0] | s_H1[t][u][1] | s_H1[t][u][2] | s_H1[t][u][3];
       const u64 h0 = s_H0[t][u][0] | s_H0[t][u][1] | s_H0[t][u][2] | s_H0[t][u][3];
-      if (h1 != 0 && h0 != 0) atomicOr(&s_live[t], 1u << u);
+      if (h1 != 0 && h0 != 0) {
+        atomicOr(&s_live[t], 1u << u);
+        // The screen runs on one cell per triple; the one whose smaller
+        // side is largest rejects most (on the benchmark pool the lowest
+        // live cell lets ~1.6% of candidates through, this one ~none).
+        int n1 = 0, n0 = 0;
+        for (int w = 0; w < 4; w++) {
+          n1 += __popcll(s_H1[t][u][w]);
+          n0 += __popcll(s_H0[t][u][w]);
+        }
+        atomicMax(&s_best[t], (static_cast<u32>(n1 < n0 ? n1 : n0) << 3) |
+                                  static_cast<u32>(7 - u));
+      }
     }
     __syncthreads();
 
-    // Per-thread runs of K consecutive pairs: one decode per run, cheap
-    // lexicographic increments inside (a decode costs ~40 ops, the
-    // increment ~4). Runs rarely cross triple boundaries (re-locate
-    // handles it).
-    constexpr int K = 4;
-    const i64 nruns = (total_pairs + K - 1) / K;
-    int it = 0;
-    for (i64 run = threadIdx.x; run < nruns; run += blockDim.x) {
-      if (((it++) & 15) == 0 && !args.count_all && dev_abort(ctl)) break;
-      i64 idx = run * K;
-      const i64 idx_end = idx + K < total_pairs ? idx + K : total_pairs;
+    // Row-segment walk. Consecutive lanes take consecutive rows d2 of one
+    // segment column: a wave mostly shares t (same-address reads of the
+    // prefix cells) and its lanes read consecutive pool rows, which the
+    // 48 B stride keeps conflict-free.
+    const int L = __builtin_amdgcn_readfirstlane(s_seg);
+    const int total_tasks = s_tpre[TB];
+    int since_poll = 0;
+    for (int task = threadIdx.x; task < total_tasks; task += blockDim.x) {
+      if (!args.count_all) {
+        // Abort poll once per 64 pairs walked, as the flat walk did.
+        since_poll += L;
+        if (since_poll >= 64) {
+          since_poll = 0;
+          if (dev_abort(ctl)) break;
+        }
+      }
       int t = 0;
-      while (s_prefix[t + 1] <= idx) t++;
-      int m = s_m[t];
-      int cgate = s_c[t];
-      i64 q = s_lo[t] + (idx - s_prefix[t]);
-      int d2, e2;
-      dev_decode_pair(q, m, &d2, &e2);
+      while (s_tpre[t + 1] <= task) t++;
+      const int m = s_m[t];
+      int d2 = task - s_tpre[t];
+      int s0 = 0;  // first gap (e2 - d2 - 1) of the segment
+      for (int rows = m - 1; d2 >= rows; rows -= L) {
+        d2 -= rows;
+        s0 += L;
+      }
+      // Flat pair index of segment position 0: S(d2) + s0. Position i is
+      // the pair (d2, d2 + 1 + s0 + i). Clip positions to the row's end and
+      // to the triple's [lo, hi) window — per task, never per pair.
+      const int q_seg = d2 * m - d2 * (d2 + 1) / 2 + s0;
+      const int lo = static_cast<int>(s_lo[t]);
+      const int i_lo = lo > q_seg ? lo - q_seg : 0;
+      int i_hi = m - 1 - d2 - s0;
+      if (i_hi > L) i_hi = L;
+      if (i_hi > s_hi[t] - q_seg) i_hi = s_hi[t] - q_seg;
+      if (i_lo >= i_hi) continue;
+      u32 valid = ((1u << i_hi) - 1u) & ~((1u << i_lo) - 1u);  // i_hi <= 16
+      const int d = s_c[t] + 1 + d2;
+      const int e_first = d + 1 + s0;  // gate at position 0
+      if (args.excl != 0) {
+        // An excluded d drops the whole row; excluded e's (ids < 64 only)
+        // drop out of the position mask with one shift per task.
+        if (d < 64 && ((args.excl >> d) & 1)) continue;
+        if (e_first < 64) valid &= ~static_cast<u32>(args.excl >> e_first);
+      }
+      local_eval += __popc(valid);
 
-      for (; idx < idx_end; idx++) {
-        if (idx >= s_prefix[t + 1]) {
-          // Crossed into the next non-empty triple.
-          do { t++; } while (s_prefix[t + 1] <= idx);
-          m = s_m[t];
-          cgate = s_c[t];
-          q = s_lo[t] + (idx - s_prefix[t]);
-          dev_decode_pair(q, m, &d2, &e2);
+      // d side, once per task: the screen cell's forced-1 / forced-0 sets
+      // split by td (A = with d, N = without d), 32 registers. A cell that
+      // is not live has one side empty and rejects nothing, so live == 0
+      // (s_best then names cell 7) needs no special case: every pair goes
+      // on to the solver, as before.
+      const u32 live = s_live[t];
+      const int u0 = 7 - static_cast<int>(s_best[t] & 7u);
+      u32 A1[8], A0[8], N1[8], N0[8];
+#pragma unroll
+      for (int w = 0; w < 4; w++) {
+        const u64 tdw = s_pool[d * PSTR + w];
+        const u64 h1 = s_H1[t][u0][w], h0 = s_H0[t][u0][w];
+        const u64 a1 = h1 & tdw, a0 = h0 & tdw;
+        const u64 n1 = h1 ^ a1, n0 = h0 ^ a0;
+        A1[2 * w] = static_cast<u32>(a1);
+        A1[2 * w + 1] = static_cast<u32>(a1 >> 32);
+        A0[2 * w] = static_cast<u32>(a0);
+        A0[2 * w + 1] = static_cast<u32>(a0 >> 32);
+        N1[2 * w] = static_cast<u32>(n1);
+        N1[2 * w + 1] = static_cast<u32>(n1 >> 32);
+        N0[2 * w] = static_cast<u32>(n0);
+        N0[2 * w + 1] = static_cast<u32>(n0 >> 32);
+      }
+
+      // e side: 8 positions per step, one bit per position whose cell u0
+      // has no quadrant holding both forced-1 and forced-0 content. All
+      // four quadrants are tested without a branch: on the benchmark pool
+      // a single quadrant rejects only ~40% of the candidates (the four
+      // together ~99%), so a wave almost never agrees on an early exit.
+      // No exclusion and no clipping per pair; reads past the row's end
+      // are masked by `valid`.
+      u32 pend = 0;
+      const u64* pe = &s_pool[e_first * PSTR];
+#pragma unroll 1
+      for (int base = 0; base < L; base += 8) {
+        if (((valid >> base) & 0xffu) == 0) continue;
+        u32 bits = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          // Pool rows start 16 B aligned (48 B stride): two ds_read_b128.
+          const lds_u32x4* p =
+              reinterpret_cast<const lds_u32x4*>(pe + (base + j) * PSTR);
+          const lds_u32x4 lo4 = p[0], hi4 = p[1];
+          const u32 te[8] = {lo4.x, lo4.y, lo4.z, lo4.w,
+                             hi4.x, hi4.y, hi4.z, hi4.w};
+          u32 x11_1 = A1[0] & te[0], x11_0 = A0[0] & te[0];
+          u32 x01_1 = N1[0] & te[0], x01_0 = N0[0] & te[0];
+          u32 x10_1 = A1[0] & ~te[0], x10_0 = A0[0] & ~te[0];
+          u32 x00_1 = N1[0] & ~te[0], x00_0 = N0[0] & ~te[0];
+#pragma unroll
+          for (int k = 1; k < 8; k++) {
+            x11_1 = dev_and_or(A1[k], te[k], x11_1);
+            x11_0 = dev_and_or(A0[k], te[k], x11_0);
+            x01_1 = dev_and_or(N1[k], te[k], x01_1);
+            x01_0 = dev_and_or(N0[k], te[k], x01_0);
+            x10_1 = dev_andn_or(A1[k], te[k], x10_1);
+            x10_0 = dev_andn_or(A0[k], te[k], x10_0);
+            x00_1 = dev_andn_or(N1[k], te[k], x00_1);
+            x00_0 = dev_andn_or(N0[k], te[k], x00_0);
+          }
+          // min(a, b) != 0 <=> both sides non-empty; kept arithmetic so
+          // the four tests do not turn into divergent branches.
+          const u32 conflict = min(x11_1, x11_0) | min(x10_1, x10_0) |
+                               min(x01_1, x01_0) | min(x00_1, x00_0);
+          bits |= static_cast<u32>(conflict == 0) << j;
         }
-        const int d = cgate + 1 + d2, e = cgate + 1 + e2;
-        bool skip = false;
-        if (args.excl != 0) {
-          skip = (d < 64 && ((args.excl >> d) & 1)) ||
-                 (e < 64 && ((args.excl >> e) & 1));
+        pend |= bits << base;
+      }
+      pend &= valid;
+
+      // Rare path: the same test on the remaining live cells, then the
+      // solver. The screen only ever passes too much.
+      while (pend != 0) {
+        const int i = __ffs(pend) - 1;
+        pend &= pend - 1;
+        const int e = e_first + i;
+        u64 td_[4], te_[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          td_[w] = s_pool[d * PSTR + w];
+          te_[w] = s_pool[e * PSTR + w];
         }
-        if (!skip) {
-          local_eval++;
-          const u64* td = &s_pool[d * PSTR];
-          const u64* te = &s_pool[e * PSTR];
-          u64 td_[4], te_[4];
+        bool ok = true;
+        for (u32 lm = live & ~(1u << u0); lm != 0; lm &= lm - 1) {
+          const int u = __ffs(lm) - 1;
+          u64 r11_1 = 0, r10_1 = 0, r01_1 = 0, r00_1 = 0;
+          u64 r11_0 = 0, r10_0 = 0, r01_0 = 0, r00_0 = 0;
 #pragma unroll
           for (int w = 0; w < 4; w++) {
-            td_[w] = td[w];
-            te_[w] = te[w];
+            const u64 h1 = s_H1[t][u][w];
+            const u64 h0 = s_H0[t][u][w];
+            // x & ~y == x ^ (x & y): avoids materializing ~td/~te.
+            const u64 a1 = h1 & td_[w];
+            const u64 na1 = h1 ^ a1;
+            const u64 a0 = h0 & td_[w];
+            const u64 na0 = h0 ^ a0;
+            const u64 x11_1 = a1 & te_[w];
+            const u64 x01_1 = na1 & te_[w];
+            const u64 x11_0 = a0 & te_[w];
+            const u64 x01_0 = na0 & te_[w];
+            r11_1 |= x11_1;
+            r10_1 |= a1 ^ x11_1;
+            r01_1 |= x01_1;
+            r00_1 |= na1 ^ x01_1;
+            r11_0 |= x11_0;
+            r10_0 |= a0 ^ x11_0;
+            r01_0 |= x01_0;
+            r00_0 |= na0 ^ x01_0;
           }
-
-          bool ok = true;
-          for (u32 lm = s_live[t]; lm != 0; lm &= lm - 1) {
-            const int u = __ffs(lm) - 1;
-            u64 r11_1 = 0, r10_1 = 0, r01_1 = 0, r00_1 = 0;
-            u64 r11_0 = 0, r10_0 = 0, r01_0 = 0, r00_0 = 0;
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-              const u64 h1 = s_H1[t][u][w];
-              const u64 h0 = s_H0[t][u][w];
-              // x & ~y == x ^ (x & y): avoids materializing ~td/~te.
-              const u64 a1 = h1 & td_[w];
-              const u64 na1 = h1 ^ a1;
-              const u64 a0 = h0 & td_[w];
-              const u64 na0 = h0 ^ a0;
-              const u64 x11_1 = a1 & te_[w];
-              const u64 x01_1 = na1 & te_[w];
-              const u64 x11_0 = a0 & te_[w];
-              const u64 x01_0 = na0 & te_[w];
-              r11_1 |= x11_1;
-              r10_1 |= a1 ^ x11_1;
-              r01_1 |= x01_1;
-              r00_1 |= na1 ^ x01_1;
-              r11_0 |= x11_0;
-              r10_0 |= a0 ^ x11_0;
-              r01_0 |= x01_0;
-              r00_0 |= na0 ^ x01_0;
-            }
-            if ((r11_1 && r11_0) || (r10_1 && r10_0) || (r01_1 && r01_0) ||
-                (r00_1 && r00_0)) {
-              ok = false;
-              break;
-            }
-          }
-          if (ok) {
-            scan5_handle_survivor(args, ctl, s_pool, s_abc[t], s_base[t] + q,
-                                  d, e);
+          if ((r11_1 && r11_0) || (r10_1 && r10_0) || (r01_1 && r01_0) ||
+              (r00_1 && r00_0)) {
+            ok = false;
+            break;
           }
         }
-        // Next pair in lexicographic order.
-        q++;
-        e2++;
-        if (e2 >= m) {
-          d2++;
-          e2 = d2 + 1;
+        if (ok) {
+          scan5_handle_survivor(args, ctl, s_pool, s_abc[t],
+                                s_base[t] + q_seg + i, d, e);
         }
       }
     }

@@ -128,7 +128,7 @@ ScanResult cpu_scan5(const ScanRequest& rq, i64 begin, i64 end) {
       if (lut5_p_masks(tt, T1, T0, &p1, &p0)) {
         u8 fo, fi;
         int split;
-        u64 rnd = hash_mix64(rq.seed ^ static_cast<u64>(i));
+        u64 rnd = scan_rnd(rq.seed, static_cast<u64>(i));
         if (lut5_solve_from_p(p1, p0, rnd, &fo, &fi, &split) && !rq.count_all) {
           const u8* sp = SPLITS5[split];
           out.found = true;

@@ -69,4 +69,11 @@ SBG_HD inline u64 hash_mix64(u64 z) {
   return z ^ (z >> 31);
 }
 
+// Random word of the candidate with flat rank idx in a seeded scan. The
+// 5-LUT kernel and cpu_scan5 both take it from here, so a given (seed,
+// combination) yields the same decomposition on either engine.
+SBG_HD inline u64 scan_rnd(u64 seed, u64 idx) {
+  return hash_mix64(seed ^ (idx * 0x9E3779B97F4A7C15ULL));
+}
+
 }  // namespace sbg

@@ -57,10 +57,14 @@ def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
     return _core.Engine(o, ctx)
 
 
-def scan(engine, k, state, target, mask, begin, end, seed=0, count_all=False):
+def scan(engine, k, state, target, mask, begin, end, seed=0, count_all=False,
+         excl=0):
     """Runs a 3/5/7-LUT combination scan over [begin, end).
 
-    Returns (found, res[10], evaluated). res layout matches the
+    excl is a bitmask of gate ids < 64 that no reported or counted
+    combination may contain (the 3-LUT scan ignores it, as the reference
+    does). Returns (found, res[10], evaluated). res layout matches the
     reference's wire format (see sbg/scan.hpp).
     """
-    return engine.scan_pool(k, state, target, mask, begin, end, seed, count_all)
+    return engine.scan_pool(k, state, target, mask, begin, end, seed, count_all,
+                            excl)

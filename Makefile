@@ -25,7 +25,8 @@ LDFLAGS    := -shared -fPIC
 
 HOST_SRCS  := $(wildcard $(SRC)/host/*.cpp)
 HOST_OBJS  := $(patsubst $(SRC)/host/%.cpp,$(BUILD)/host_%.o,$(HOST_SRCS))
-HIP_OBJS   := $(BUILD)/kernels.o
+HIP_SRCS   := $(wildcard $(SRC)/hip/*.hip)
+HIP_OBJS   := $(patsubst $(SRC)/hip/%.hip,$(BUILD)/hip_%.o,$(HIP_SRCS))
 EXT        := sboxgates_amd/_core$(EXT_SUFFIX)
 CLI        := bin/sboxgates
 
@@ -40,7 +41,7 @@ $(BUILD):
 $(BUILD)/host_%.o: $(SRC)/host/%.cpp | $(BUILD)
 	$(HIPCC) -x c++ $(CXXFLAGS) -c $< -o $@
 
-$(BUILD)/kernels.o: $(SRC)/hip/kernels.hip | $(BUILD)
+$(BUILD)/hip_%.o: $(SRC)/hip/%.hip | $(BUILD)
 	$(HIPCC) $(CXXFLAGS) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/bindings.o: $(SRC)/bindings.cpp | $(BUILD)

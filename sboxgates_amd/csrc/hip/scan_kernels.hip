@@ -1,0 +1,949 @@
+// scan_kernels.hip — CDNA4 (gfx950) one-shot kernels for the 3/5/7-LUT and
+// k=4 candidate scans, plus the GpuEngine host wrapper. Shared device code:
+// scan_device.hpp; persistent k=4 service: scan_service.hip.
+//
+// Design (MI355X-first; see SURVEY.md §2.3 and the repo README):
+//  * One thread evaluates one candidate combination on 256-bit truth
+//    tables held as 4 u64 words. The reference runs these scans as CPU
+//    loops across MPI ranks (lut.c:116-487); here the per-candidate
+//    feasibility test is restructured as incremental cell algebra
+//    (sbg/lutcover.hpp) with a per-u early exit.
+//  * The live gate pool (<= 500 x 32 B = 16 KB) is staged in LDS once per
+//    workgroup; the shared outer-prefix cells (8 for 5-LUT, 16 for 7-LUT)
+//    are computed once per prefix and broadcast-read from LDS, so the
+//    inner loop touches only the candidate's own 2-3 tables.
+//  * Work distribution: workgroups pull combination *prefixes* (triples
+//    for K5, quadruples for K7) from a device-scope atomic queue — the
+//    per-prefix work varies by orders of magnitude, and the dequeue
+//    primitive costs ~0.25-1 us (MI355X_MICROARch price list), negligible
+//    against per-prefix work. Grids are sized >> 256 CUs.
+//  * Early exit: winner election by atomicCAS on a device-scope lock; an
+//    agent-scope abort flag (sc1, L1-bypassing load) is polled on a coarse
+//    cadence. Any valid winner is acceptable (the reference is equally
+//    nondeterministic across ranks, lut.c:213-218).
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <string>
+
+#include "sbg/comb.hpp"
+#include "scan_device.hpp"
+#include "scan_service.hpp"
+
+namespace sbg {
+
+namespace {
+
+// Batch sizes and split factors, shared by the kernels and the host code
+// that sizes their grids.
+constexpr int TB = 8;        // k_scan5: triple prefixes per dequeue
+constexpr int QB = 4;        // k_scan7_filter: quad units per dequeue
+constexpr u64 FM_SPLIT = 8;  // k_scan7_assign: threads per (hit, ordering)
+// k_scan7_filter: candidates one dequeue unit should hold; the host slices
+// quads until a scan has about one unit per this many candidates.
+constexpr i64 SLICE_UNIT = 8 * SCAN_BLOCK;
+
+// ---------------------------------------------------------------------------
+// K2 — 3-LUT scan. Grid-stride over combination ranks; per-thread decode by
+// binary search on closed-form binomials; cells evaluated directly (the
+// reference's serial rank-0 loop, lut.c:501-523).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan3(ScanArgs args) {
+  __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
+  load_pool_lds(s_pool, args.pool, args.n);
+  __syncthreads();
+
+  DevCtl* ctl = args.ctl;
+  const i64 stride = static_cast<i64>(gridDim.x) * blockDim.x;
+  const i64 idx0 =
+      args.begin + blockIdx.x * static_cast<i64>(blockDim.x) + threadIdx.x;
+  const u64 local_eval = walk_triples(
+      s_pool, args.n, args.T1, args.T0, args.count_all, ctl, idx0, args.end,
+      stride, [&](i64 idx, int a, int b, int c, u32 p1, u32 p0) {
+        u8 func = lut3_function_from_p(p1, p0, scan_rnd(args.seed, idx));
+        if (args.count_all || func == 0) return false;
+        u16 res[10] = {};
+        res[0] = func;
+        res[1] = static_cast<u16>(a);
+        res[2] = static_cast<u16>(b);
+        res[3] = static_cast<u16>(c);
+        dev_publish(ctl, res);
+        return true;
+      });
+  block_add_evaluated(ctl, local_eval);
+}
+
+// K1c — gate-mode step-4 triple scan, one-shot launch (Scan4Match in
+// scan_device.hpp is the per-triple function search).
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan4(ScanArgs args) {
+  __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
+  __shared__ alignas(16) u8 s_bitmap[MATCHER_BITMAP_BYTES];
+  __shared__ u8 s_funs[256];
+  __shared__ int s_count;
+  load_pool_lds(s_pool, args.pool, args.n);
+  load_matcher_lds(s_bitmap, s_funs, &s_count, args.matcher);
+  __syncthreads();
+
+  DevCtl* ctl = args.ctl;
+  const i64 stride = static_cast<i64>(gridDim.x) * blockDim.x;
+  const i64 idx0 =
+      args.begin + blockIdx.x * static_cast<i64>(blockDim.x) + threadIdx.x;
+  const u64 local_eval = walk_triples(
+      s_pool, args.n, args.T1, args.T0, args.count_all, ctl, idx0, args.end,
+      stride, Scan4Match{s_bitmap, s_funs, s_count, args.count_all, ctl});
+  block_add_evaluated(ctl, local_eval);
+}
+
+// ---------------------------------------------------------------------------
+// K3 — 5-LUT scan. Workgroups dequeue triple prefixes; the 8 prefix cells
+// (masked with target-1/target-0) are computed cooperatively into LDS; each
+// thread then takes row segments — one d, a few consecutive e — hoists the
+// d side of the most balanced live cell, screens the e's against it,
+// sends what passes through the remaining live cells, and runs the
+// 2-coloring decomposition solver on survivors (replacing the reference's
+// 10 x 256-function brute force, lut.c:174-246).
+// ---------------------------------------------------------------------------
+
+// (a & b) | acc in one VALU instruction. Written out because the compiler
+// rebalances a plain C chain of these into v_and_b32 pairs feeding
+// v_or3_b32 (11 instructions per 8-dword reduction instead of 8) and keeps
+// vectorized copies of the loop-invariant operands.
+__device__ __forceinline__ u32 dev_and_or(u32 a, u32 b, u32 acc) {
+  u32 r;
+  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc));
+  return r;
+}
+
+// (a & ~b) | acc, likewise one instruction (gfx950's three-input bit op,
+// truth table 0xba), so ~te is never materialised.
+__device__ __forceinline__ u32 dev_andn_or(u32 a, u32 b, u32 acc) {
+  u32 r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba"
+      : "=v"(r) : "v"(a), "v"(b), "v"(acc));
+  return r;
+}
+
+// 16-byte LDS read of a pool row half (rows are u64 words at a 16 B
+// aligned stride; may_alias makes the differently-typed read well defined).
+typedef u32 lds_u32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
+
+// Survivor handling for k_scan5 (rare path; noinline keeps its registers
+// out of the hot loop's budget).
+__device__ __attribute__((noinline)) void scan5_handle_survivor(
+    const ScanArgs& args, DevCtl* ctl, const u64* s_pool, const u16* abc,
+    i64 rank, int d, int e) {
+  ttable tt5[5];
+  const int ids[5] = {abc[0], abc[1], abc[2], d, e};
+  for (int j = 0; j < 5; j++) {
+    for (int w = 0; w < 4; w++) tt5[j].w[w] = s_pool[ids[j] * PSTR + w];
+  }
+  u32 p1, p0;
+  if (!lut5_p_masks(tt5, args.T1, args.T0, &p1, &p0)) return;
+  u8 fo, fi;
+  int split;
+  if (!lut5_solve_from_p(p1, p0, scan_rnd(args.seed, rank), &fo, &fi, &split)) {
+    return;
+  }
+  if (args.count_all) return;
+  const u16 nums[5] = {abc[0], abc[1], abc[2], static_cast<u16>(d),
+                       static_cast<u16>(e)};
+  const u8* sp = SPLITS5[split];
+  u16 res[10] = {};
+  res[0] = fo;
+  res[1] = fi;
+  for (int j = 0; j < 3; j++) res[2 + j] = nums[sp[j]];
+  res[5] = nums[sp[3]];
+  res[6] = nums[sp[4]];
+  dev_publish(ctl, res);
+}
+
+__global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
+  // Triple batching: one dequeue + one cooperative prefix-cell build + one
+  // barrier per TB triples (measured at TB=1: 48% of wave time parked on
+  // the per-triple barriers; batching amortizes them 8x).
+  //
+  // The row screen reads whole segments of up to SEG_MAX pool rows without
+  // per-pair bounds tests; the pad rows keep a segment that starts at the
+  // pool's last gate inside the array (their content is masked out).
+  constexpr int SEG_MAX = 16;
+  __shared__ alignas(16) u64 s_pool[(MAX_GATES + SEG_MAX) * PSTR];
+  __shared__ alignas(16) u64 s_H1[TB][8][4];
+  __shared__ alignas(16) u64 s_H0[TB][8][4];
+  __shared__ i64 s_base[TB];     // flat-rank base of each triple
+  __shared__ i64 s_lo[TB], s_prefix[TB + 1];
+  __shared__ int s_hi[TB];       // window end (flat pair index) per triple
+  __shared__ int s_tpre[TB + 1]; // prefix sums of row-segment task counts
+  __shared__ int s_seg;          // segment length of this batch
+  __shared__ int s_m[TB];
+  __shared__ u16 s_abc[TB][3];
+  __shared__ u32 s_live[TB];     // cells with both forced-1 and forced-0
+                                 // content; only these can contradict
+  __shared__ u32 s_best[TB];     // (min side popcount << 3 | 7 - u) of the
+                                 // most balanced live cell: the screen cell
+  __shared__ i64 s_batch;        // first triple index of the batch
+  __shared__ int s_stop;         // all triples past range end
+
+  const int n = args.n;
+  load_pool_lds(s_pool, args.pool, n);
+
+  DevCtl* ctl = args.ctl;
+  const i64 total3 = cf3(n);
+  u64 local_eval = 0;
+
+  for (;;) {
+    const i64 batch_base =
+        dequeue_batch(ctl, TB, args.count_all, false, &s_batch);
+    if (batch_base < 0) break;
+
+    // Threads 0..TB-1 decode one triple each and compute its pair window.
+    if (threadIdx.x < TB) {
+      const int t = threadIdx.x;
+      PrefixWindow<3> p = decode_prefix_window<3>(batch_base + t, total3, args);
+      drop_dead_prefix(p, args);
+      s_base[t] = p.base;
+      s_lo[t] = p.lo;
+      s_hi[t] = static_cast<int>(p.hi);  // <= C(m, 2) < 2^17
+      s_m[t] = p.m;
+      for (int j = 0; j < 3; j++) s_abc[t][j] = static_cast<u16>(p.ids[j]);
+      s_prefix[t + 1] = p.hi - p.lo;  // count, turned into prefix sums below
+      if (t == 0) s_prefix[0] = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      // Prefix-sum the TB pair counts. Termination: triple flat-rank bases
+      // increase with the triple index, so once the batch's first triple
+      // is past the range end (or past the triple space), every later
+      // batch is too.
+      s_stop = (batch_base >= total3 || s_base[0] >= args.end) ? 1 : 0;
+      // Row-segment tasks. A task is (triple, row d2, segment): the pairs
+      // (d2, e2) with gap e2 - d2 - 1 in [s0, s0 + L). Segment s0 exists for
+      // the rows d2 < m - 1 - s0, so a triple has sum_s (m - 1 - s * L)
+      // tasks. L follows the batch's longest row. Long rows get SEG_MAX:
+      // measured at pool 450, 16-pair segments beat 32-pair ones by 2.6%
+      // (half the ragged-tail waste for twice the d-side hoists). Short
+      // rows (the search's small pools) get 4 pairs, the flat walk's old
+      // run length: those scans are dominated by survivors going through
+      // the solver one after another in their lane, and 8-pair segments
+      // made the AES bit-0 search 15% slower than 4-pair ones.
+      int mmax = 0;
+      for (int t = 0; t < TB; t++) {
+        if (s_prefix[t + 1] != 0 && s_m[t] > mmax) mmax = s_m[t];
+      }
+      const int lg = mmax > 40 ? 4 : 2;
+      const int L = 1 << lg;  // SEG_MAX at most
+      s_seg = L;
+      s_tpre[0] = 0;
+      for (int t = 0; t < TB; t++) {
+        int cnt = 0;
+        if (s_prefix[t + 1] != 0) {
+          const int rows = s_m[t] - 1;
+          const int ns = (rows + L - 1) >> lg;
+          cnt = ns * rows - L * (ns * (ns - 1) / 2);
+        }
+        s_tpre[t + 1] = s_tpre[t] + cnt;
+      }
+      for (int t = 0; t < TB; t++) s_prefix[t + 1] += s_prefix[t];
+    }
+    __syncthreads();
+    if (s_stop) break;
+    const i64 total_pairs = s_prefix[TB];
+    if (total_pairs == 0) continue;
+
+    build_prefix_cells<3, TB>(s_pool, s_abc, s_prefix, args.T1, args.T0, s_H1,
+                              s_H0);
+    if (threadIdx.x < TB) s_best[threadIdx.x] = 0;
+    if (mark_live_cells<3, TB>(s_H1, s_H0, s_live)) {
+      // The screen runs on one cell per triple; the one whose smaller
+      // side is largest rejects most (on the benchmark pool the lowest
+      // live cell lets ~1.6% of candidates through, this one ~none).
+      const int t = threadIdx.x >> 3;
+      const int u = threadIdx.x & 7;
+      int n1 = 0, n0 = 0;
+      for (int w = 0; w < 4; w++) {
+        n1 += __popcll(s_H1[t][u][w]);
+        n0 += __popcll(s_H0[t][u][w]);
+      }
+      atomicMax(&s_best[t], (static_cast<u32>(n1 < n0 ? n1 : n0) << 3) |
+                                static_cast<u32>(7 - u));
+    }
+    __syncthreads();
+
+    // Row-segment walk. Consecutive lanes take consecutive rows d2 of one
+    // segment column: a wave mostly shares t (same-address reads of the
+    // prefix cells) and its lanes read consecutive pool rows, which the
+    // 48 B stride keeps conflict-free.
+    const int L = __builtin_amdgcn_readfirstlane(s_seg);
+    const int total_tasks = s_tpre[TB];
+    int since_poll = 0;
+    for (int task = threadIdx.x; task < total_tasks; task += blockDim.x) {
+      if (!args.count_all) {
+        // Abort poll once per 64 pairs walked, as the flat walk did.
+        since_poll += L;
+        if (since_poll >= 64) {
+          since_poll = 0;
+          if (dev_abort(ctl)) break;
+        }
+      }
+      int t = 0;
+      while (s_tpre[t + 1] <= task) t++;
+      const int m = s_m[t];
+      int d2 = task - s_tpre[t];
+      int s0 = 0;  // first gap (e2 - d2 - 1) of the segment
+      for (int rows = m - 1; d2 >= rows; rows -= L) {
+        d2 -= rows;
+        s0 += L;
+      }
+      // Flat pair index of segment position 0: S(d2) + s0. Position i is
+      // the pair (d2, d2 + 1 + s0 + i). Clip positions to the row's end and
+      // to the triple's [lo, hi) window — per task, never per pair.
+      const int q_seg = d2 * m - d2 * (d2 + 1) / 2 + s0;
+      const int lo = static_cast<int>(s_lo[t]);
+      const int i_lo = lo > q_seg ? lo - q_seg : 0;
+      int i_hi = m - 1 - d2 - s0;
+      if (i_hi > L) i_hi = L;
+      if (i_hi > s_hi[t] - q_seg) i_hi = s_hi[t] - q_seg;
+      if (i_lo >= i_hi) continue;
+      u32 valid = ((1u << i_hi) - 1u) & ~((1u << i_lo) - 1u);  // i_hi <= 16
+      // c + 1 + d2 with c = n - 1 - m (measured: fetching c from s_abc
+      // here, one more LDS read per task, cost 1% on the bench).
+      const int d = n - m + d2;
+      const int e_first = d + 1 + s0;  // gate at position 0
+      if (args.excl != 0) {
+        // An excluded d drops the whole row; excluded e's (ids < 64 only)
+        // drop out of the position mask with one shift per task.
+        if (dev_excluded(args.excl, d)) continue;
+        if (e_first < 64) valid &= ~static_cast<u32>(args.excl >> e_first);
+      }
+      local_eval += __popc(valid);
+
+      // d side, once per task: the screen cell's forced-1 / forced-0 sets
+      // split by td (A = with d, N = without d), 32 registers. A cell that
+      // is not live has one side empty and rejects nothing, so live == 0
+      // (s_best then names cell 7) needs no special case: every pair goes
+      // on to the solver, as before.
+      const u32 live = s_live[t];
+      const int u0 = 7 - static_cast<int>(s_best[t] & 7u);
+      u32 A1[8], A0[8], N1[8], N0[8];
+#pragma unroll
+      for (int w = 0; w < 4; w++) {
+        const u64 tdw = s_pool[d * PSTR + w];
+        const u64 h1 = s_H1[t][u0][w], h0 = s_H0[t][u0][w];
+        const u64 a1 = h1 & tdw, a0 = h0 & tdw;
+        const u64 n1 = h1 ^ a1, n0 = h0 ^ a0;
+        A1[2 * w] = static_cast<u32>(a1);
+        A1[2 * w + 1] = static_cast<u32>(a1 >> 32);
+        A0[2 * w] = static_cast<u32>(a0);
+        A0[2 * w + 1] = static_cast<u32>(a0 >> 32);
+        N1[2 * w] = static_cast<u32>(n1);
+        N1[2 * w + 1] = static_cast<u32>(n1 >> 32);
+        N0[2 * w] = static_cast<u32>(n0);
+        N0[2 * w + 1] = static_cast<u32>(n0 >> 32);
+      }
+
+      // e side: 8 positions per step, one bit per position whose cell u0
+      // has no quadrant holding both forced-1 and forced-0 content. All
+      // four quadrants are tested without a branch: on the benchmark pool
+      // a single quadrant rejects only ~40% of the candidates (the four
+      // together ~99%), so a wave almost never agrees on an early exit.
+      // No exclusion and no clipping per pair; reads past the row's end
+      // are masked by `valid`.
+      u32 pend = 0;
+      const u64* pe = &s_pool[e_first * PSTR];
+#pragma unroll 1
+      for (int base = 0; base < L; base += 8) {
+        if (((valid >> base) & 0xffu) == 0) continue;
+        u32 bits = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          // Pool rows start 16 B aligned (48 B stride): two ds_read_b128.
+          const lds_u32x4* p =
+              reinterpret_cast<const lds_u32x4*>(pe + (base + j) * PSTR);
+          const lds_u32x4 lo4 = p[0], hi4 = p[1];
+          const u32 te[8] = {lo4.x, lo4.y, lo4.z, lo4.w,
+                             hi4.x, hi4.y, hi4.z, hi4.w};
+          u32 x11_1 = A1[0] & te[0], x11_0 = A0[0] & te[0];
+          u32 x01_1 = N1[0] & te[0], x01_0 = N0[0] & te[0];
+          u32 x10_1 = A1[0] & ~te[0], x10_0 = A0[0] & ~te[0];
+          u32 x00_1 = N1[0] & ~te[0], x00_0 = N0[0] & ~te[0];
+#pragma unroll
+          for (int k = 1; k < 8; k++) {
+            x11_1 = dev_and_or(A1[k], te[k], x11_1);
+            x11_0 = dev_and_or(A0[k], te[k], x11_0);
+            x01_1 = dev_and_or(N1[k], te[k], x01_1);
+            x01_0 = dev_and_or(N0[k], te[k], x01_0);
+            x10_1 = dev_andn_or(A1[k], te[k], x10_1);
+            x10_0 = dev_andn_or(A0[k], te[k], x10_0);
+            x00_1 = dev_andn_or(N1[k], te[k], x00_1);
+            x00_0 = dev_andn_or(N0[k], te[k], x00_0);
+          }
+          // min(a, b) != 0 <=> both sides non-empty; kept arithmetic so
+          // the four tests do not turn into divergent branches.
+          const u32 conflict = min(x11_1, x11_0) | min(x10_1, x10_0) |
+                               min(x01_1, x01_0) | min(x00_1, x00_0);
+          bits |= static_cast<u32>(conflict == 0) << j;
+        }
+        pend |= bits << base;
+      }
+      pend &= valid;
+
+      // Rare path: the same test on the remaining live cells, then the
+      // solver. The screen only ever passes too much.
+      while (pend != 0) {
+        const int i = __ffs(pend) - 1;
+        pend &= pend - 1;
+        const int e = e_first + i;
+        u64 td_[4], te_[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          td_[w] = s_pool[d * PSTR + w];
+          te_[w] = s_pool[e * PSTR + w];
+        }
+        bool ok = true;
+        for (u32 lm = live & ~(1u << u0); lm != 0; lm &= lm - 1) {
+          const int u = __ffs(lm) - 1;
+          u64 r11_1 = 0, r10_1 = 0, r01_1 = 0, r00_1 = 0;
+          u64 r11_0 = 0, r10_0 = 0, r01_0 = 0, r00_0 = 0;
+#pragma unroll
+          for (int w = 0; w < 4; w++) {
+            const u64 h1 = s_H1[t][u][w];
+            const u64 h0 = s_H0[t][u][w];
+            // x & ~y == x ^ (x & y): avoids materializing ~td/~te.
+            const u64 a1 = h1 & td_[w];
+            const u64 na1 = h1 ^ a1;
+            const u64 a0 = h0 & td_[w];
+            const u64 na0 = h0 ^ a0;
+            const u64 x11_1 = a1 & te_[w];
+            const u64 x01_1 = na1 & te_[w];
+            const u64 x11_0 = a0 & te_[w];
+            const u64 x01_0 = na0 & te_[w];
+            r11_1 |= x11_1;
+            r10_1 |= a1 ^ x11_1;
+            r01_1 |= x01_1;
+            r00_1 |= na1 ^ x01_1;
+            r11_0 |= x11_0;
+            r10_0 |= a0 ^ x11_0;
+            r01_0 |= x01_0;
+            r00_0 |= na0 ^ x01_0;
+          }
+          if ((r11_1 && r11_0) || (r10_1 && r10_0) || (r01_1 && r01_0) ||
+              (r00_1 && r00_0)) {
+            ok = false;
+            break;
+          }
+        }
+        if (ok) {
+          scan5_handle_survivor(args, ctl, s_pool, s_abc[t],
+                                s_base[t] + q_seg + i, d, e);
+        }
+      }
+    }
+  }
+
+  block_add_evaluated(ctl, local_eval);
+}
+
+// ---------------------------------------------------------------------------
+// K4a — 7-LUT feasibility filter. Workgroups dequeue quadruple prefixes;
+// 16 prefix cells in LDS; threads screen (e, f, g) triples; survivors'
+// p-masks land in the hit buffer (no 100k cap — 288 GB HBM keeps the whole
+// frontier resident; overflow of the per-chunk buffer is reported and the
+// host re-scans a smaller range).
+// ---------------------------------------------------------------------------
+// Survivor handling for k_scan7_filter: exact p-mask rebuild + hit append.
+__device__ __attribute__((noinline)) void scan7_handle_survivor(
+    const ScanArgs& args, DevCtl* ctl, const u64* s_pool, const u16* abcd,
+    int e, int f, int g) {
+  ttable tt7[7];
+  const int ids[7] = {abcd[0], abcd[1], abcd[2], abcd[3], e, f, g};
+  for (int j = 0; j < 7; j++) {
+    for (int w = 0; w < 4; w++) tt7[j].w[w] = s_pool[ids[j] * PSTR + w];
+  }
+  u64 p1[2], p0[2];
+  if (!lut7_p_masks(tt7, args.T1, args.T0, p1, p0)) return;
+  if (args.count_all) return;  // bench mode: no hit materialization
+  unsigned long long slot = __hip_atomic_fetch_add(&ctl->hit_count, 1ULL,
+                                                   __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+  if (slot >= args.hit_cap) {
+    __hip_atomic_store(&ctl->overflow, 1u, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  Hit7& h = args.hits[slot];
+  h.p1[0] = p1[0];
+  h.p1[1] = p1[1];
+  h.p0[0] = p0[0];
+  h.p0[1] = p0[1];
+  for (int j = 0; j < 7; j++) h.nums[j] = static_cast<u16>(ids[j]);
+}
+
+__global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan7_filter(ScanArgs args) {
+  // Quad batching: one dequeue + one cooperative 16-cell build per QB
+  // quadruples (same barrier-amortization pattern as k_scan5).
+  __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
+  __shared__ alignas(16) u64 s_H1[QB][16][4];
+  __shared__ alignas(16) u64 s_H0[QB][16][4];
+  __shared__ i64 s_lo[QB], s_prefix[QB + 1];
+  __shared__ int s_m[QB], s_d[QB];
+  __shared__ u16 s_abcd[QB][4];
+  __shared__ u32 s_live[QB];
+  __shared__ i64 s_batch;  // first unit (quad x slice) index of the batch
+  __shared__ i64 s_first;  // flat-rank base of the batch's first quad
+  __shared__ int s_stop;
+
+  const int n = args.n;
+  load_pool_lds(s_pool, args.pool, n);
+
+  DevCtl* ctl = args.ctl;
+  const i64 total4 = cf4(n);
+  u64 local_eval = 0;
+
+  for (;;) {
+    const i64 batch_base =
+        dequeue_batch(ctl, QB, args.count_all, true, &s_batch);
+    if (batch_base < 0) break;
+
+    if (threadIdx.x < QB) {
+      const int t = threadIdx.x;
+      const int S = args.slices7;
+      const i64 unit = batch_base + t;
+      const i64 qidx = unit / S;
+      const int slice = static_cast<int>(unit % S);
+      PrefixWindow<4> p = decode_prefix_window<4>(qidx, total4, args);
+      if (S > 1 && p.hi > p.lo) {
+        // This unit covers one slice of the quad's triple window.
+        const i64 span = p.hi - p.lo;
+        const i64 per = (span + S - 1) / S;
+        const i64 s_lo2 = p.lo + per * slice;
+        const i64 s_hi2 = s_lo2 + per < p.hi ? s_lo2 + per : p.hi;
+        p.lo = s_lo2 < p.hi ? s_lo2 : p.hi;
+        p.hi = s_hi2;
+      }
+      drop_dead_prefix(p, args);
+      if (t == 0) {
+        s_first = p.base;
+        s_prefix[0] = 0;
+      }
+      s_lo[t] = p.lo;
+      s_m[t] = p.m;
+      s_d[t] = p.ids[3];
+      for (int j = 0; j < 4; j++) s_abcd[t][j] = static_cast<u16>(p.ids[j]);
+      s_prefix[t + 1] = p.hi - p.lo;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      s_stop = (batch_base / args.slices7 >= total4 || s_first >= args.end)
+                   ? 1
+                   : 0;
+      for (int t = 0; t < QB; t++) s_prefix[t + 1] += s_prefix[t];
+    }
+    __syncthreads();
+    if (s_stop) break;
+    const i64 total_trips = s_prefix[QB];
+    if (total_trips == 0) continue;
+
+    build_prefix_cells<4, QB>(s_pool, s_abcd, s_prefix, args.T1, args.T0, s_H1,
+                              s_H0);
+    mark_live_cells<4, QB>(s_H1, s_H0, s_live);
+    __syncthreads();
+
+    int it = 0;
+    for (i64 idx = threadIdx.x; idx < total_trips; idx += blockDim.x) {
+      if (((it++) & 15) == 0) {
+        if ((!args.count_all && dev_abort(ctl)) ||
+            __hip_atomic_load(&ctl->overflow, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT) != 0) {
+          break;
+        }
+      }
+      int t = 0;
+      while (s_prefix[t + 1] <= idx) t++;
+      const i64 q = s_lo[t] + (idx - s_prefix[t]);
+      const int m = s_m[t];
+      const int dgate = s_d[t];
+      int e2, f2, g2;
+      dev_decode_triple(q, m, &e2, &f2, &g2);
+      int e = dgate + 1 + e2, f = dgate + 1 + f2, g = dgate + 1 + g2;
+      if (args.excl != 0) {
+        if (dev_excluded(args.excl, e) || dev_excluded(args.excl, f) ||
+            dev_excluded(args.excl, g)) {
+          continue;
+        }
+      }
+      local_eval++;
+
+      u64 te_[4], tf_[4], tg_[4];
+#pragma unroll
+      for (int w = 0; w < 4; w++) {
+        te_[w] = s_pool[e * PSTR + w];
+        tf_[w] = s_pool[f * PSTR + w];
+        tg_[w] = s_pool[g * PSTR + w];
+      }
+
+      bool ok = true;
+      for (u32 lm = s_live[t]; lm != 0 && ok; lm &= lm - 1) {
+        const int u = __ffs(lm) - 1;
+        u64 acc1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        u64 acc0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          const u64 h1 = s_H1[t][u][w];
+          const u64 h0 = s_H0[t][u][w];
+          const u64 e1 = h1 & te_[w];
+          const u64 e0n = h1 ^ e1;
+          const u64 z1 = h0 & te_[w];
+          const u64 z0n = h0 ^ z1;
+          const u64 ef11 = e1 & tf_[w];
+          const u64 ef10 = e1 ^ ef11;
+          const u64 ef01 = e0n & tf_[w];
+          const u64 ef00 = e0n ^ ef01;
+          const u64 zf11 = z1 & tf_[w];
+          const u64 zf10 = z1 ^ zf11;
+          const u64 zf01 = z0n & tf_[w];
+          const u64 zf00 = z0n ^ zf01;
+          u64 x;
+          x = ef11 & tg_[w]; acc1[7] |= x; acc1[6] |= ef11 ^ x;
+          x = ef10 & tg_[w]; acc1[5] |= x; acc1[4] |= ef10 ^ x;
+          x = ef01 & tg_[w]; acc1[3] |= x; acc1[2] |= ef01 ^ x;
+          x = ef00 & tg_[w]; acc1[1] |= x; acc1[0] |= ef00 ^ x;
+          x = zf11 & tg_[w]; acc0[7] |= x; acc0[6] |= zf11 ^ x;
+          x = zf10 & tg_[w]; acc0[5] |= x; acc0[4] |= zf10 ^ x;
+          x = zf01 & tg_[w]; acc0[3] |= x; acc0[2] |= zf01 ^ x;
+          x = zf00 & tg_[w]; acc0[1] |= x; acc0[0] |= zf00 ^ x;
+        }
+#pragma unroll
+        for (int pp = 0; pp < 8; pp++) {
+          if (acc1[pp] && acc0[pp]) {
+            ok = false;
+            break;
+          }
+        }
+      }
+      if (!ok) continue;
+      scan7_handle_survivor(args, ctl, s_pool, s_abcd[t], e, f, g);
+    }
+  }
+
+  block_add_evaluated(ctl, local_eval);
+}
+
+// ---------------------------------------------------------------------------
+// K4b — 7-LUT function assignment over filtered hits: one thread per
+// (hit, ordering); each runs the middle-function sweep + outer 2-coloring
+// (replacing the reference's 70 x 256 x 256 brute force, lut.c:416-484).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan7_assign(
+    const Hit7* hits, unsigned long long nhits, DevCtl* ctl, u64 seed) {
+  // One thread per (hit, ordering, fm-octant): the 256-middle-function
+  // sweep splits across 8 threads (disjoint 32-function slices of the
+  // same shuffled order), which bounds the divergent tail of exhaustive
+  // items at ~32 colorings and feeds the GPU 8x more parallel slack.
+  constexpr int FM_SLICE = 256 / static_cast<int>(FM_SPLIT);
+  const u64 nitems = nhits * LUT7_NUM_ORDERINGS * FM_SPLIT;
+  const u64 stride = static_cast<u64>(gridDim.x) * blockDim.x;
+  int tick = 0;
+  for (u64 item = blockIdx.x * static_cast<u64>(blockDim.x) + threadIdx.x;
+       item < nitems; item += stride) {
+    if (((tick++) & 3) == 0 && dev_abort(ctl)) return;
+    const u64 base_item = item / FM_SPLIT;
+    const int oct = static_cast<int>(item % FM_SPLIT);
+    const Hit7& h = hits[base_item / LUT7_NUM_ORDERINGS];
+    int oidx = static_cast<int>(base_item % LUT7_NUM_ORDERINGS);
+    u8 ord[7];
+    lut7_ordering(oidx, ord);
+    u8 fo, fm, fi;
+    // rnd keyed by (hit, ordering) so the 8 octants partition the same
+    // shuffled middle-function order disjointly.
+    if (lut7_solve_ordering(h.p1, h.p0, ord, scan_rnd(seed, base_item), &fo,
+                            &fm, &fi, oct * FM_SLICE, FM_SLICE)) {
+      u16 res[10];
+      res[0] = fo;
+      res[1] = fm;
+      res[2] = fi;
+      for (int j = 0; j < 7; j++) res[3 + j] = h.nums[ord[j]];
+      dev_publish(ctl, res);
+      return;
+    }
+  }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// GpuEngine host wrapper.
+// ---------------------------------------------------------------------------
+
+struct GpuEngine::Impl {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  ttable* d_pool = nullptr;
+  DevCtl* d_ctl = nullptr;
+  Hit7* d_hits = nullptr;
+  Avail3Matcher* d_matcher = nullptr;
+  ttable* h_pool = nullptr;  // pinned staging: pageable-source async
+                             // copies cost ~100s of us on small scans
+  const Avail3Matcher* last_matcher = nullptr;  // uploaded-matcher cache
+  u64 hit_cap = 0;
+  DevCtl* h_ctl = nullptr;  // pinned staging
+  std::string name;
+  std::shared_ptr<ScanService> svc;  // lazily acquired for k=4 scans
+  bool svc_tried = false;
+  bool svc_broken = false;
+
+  ~Impl() {
+    if (d_pool != nullptr) (void)hipFree(d_pool);
+    if (d_matcher != nullptr) (void)hipFree(d_matcher);
+    if (d_ctl != nullptr) (void)hipFree(d_ctl);
+    if (d_hits != nullptr) (void)hipFree(d_hits);
+    if (h_ctl != nullptr) (void)hipHostFree(h_ctl);
+    if (h_pool != nullptr) (void)hipHostFree(h_pool);
+    if (stream != nullptr) (void)hipStreamDestroy(stream);
+  }
+
+  // One launch round trip: upload h_ctl, launch, download h_ctl, wait.
+  template <class... Params, class... Args>
+  void run(void (*kernel)(Params...), int grid, Args&&... args) {
+    SBG_HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(DevCtl),
+                                 hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(SCAN_BLOCK), 0, stream,
+                       static_cast<Params>(args)...);
+    SBG_HIP_CHECK(hipGetLastError());
+    SBG_HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(DevCtl),
+                                 hipMemcpyDeviceToHost, stream));
+    SBG_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+};
+
+// Ranks, among the np-prefixes, of the prefixes of the first and the last
+// k-combination in [begin, end): the span of the kernels' prefix queue.
+static void prefix_rank_span(int n, int k, int np, i64 begin, i64 end,
+                             i64* first, i64* last) {
+  gatenum comb[7];
+  nth_combination(begin, n, k, 0, comb);
+  *first = combination_rank(comb, np, n);
+  nth_combination(end - 1, n, k, 0, comb);
+  *last = combination_rank(comb, np, n);
+}
+
+bool gpu_available() { return gpu_count() > 0; }
+
+int gpu_count() {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess) return 0;
+  return count;
+}
+
+std::unique_ptr<GpuEngine> GpuEngine::create(int device, std::string* err) {
+  int count = 0;
+  hipError_t e = hipGetDeviceCount(&count);
+  if (e != hipSuccess || count == 0) {
+    if (err != nullptr) {
+      *err = e == hipSuccess ? "no HIP devices visible" : hipGetErrorString(e);
+    }
+    return nullptr;
+  }
+  try {
+    auto impl = std::make_unique<Impl>();
+    if (device >= 0) {
+      SBG_HIP_CHECK(hipSetDevice(device));
+      impl->device = device;
+    } else {
+      SBG_HIP_CHECK(hipGetDevice(&impl->device));
+    }
+    hipDeviceProp_t prop;
+    SBG_HIP_CHECK(hipGetDeviceProperties(&prop, impl->device));
+    impl->name = prop.name;
+    SBG_HIP_CHECK(hipStreamCreate(&impl->stream));
+    SBG_HIP_CHECK(hipMalloc(&impl->d_pool, sizeof(ttable) * MAX_GATES));
+    SBG_HIP_CHECK(hipMalloc(&impl->d_ctl, sizeof(DevCtl)));
+    SBG_HIP_CHECK(hipMalloc(&impl->d_matcher, sizeof(Avail3Matcher)));
+    SBG_HIP_CHECK(hipHostMalloc(&impl->h_ctl, sizeof(DevCtl)));
+    SBG_HIP_CHECK(hipHostMalloc(&impl->h_pool, sizeof(ttable) * MAX_GATES));
+    // Hit buffer for the 7-LUT frontier: default 16M hits (768 MB) per
+    // chunk; overridable for memory-constrained runs. Allocated lazily on
+    // the first 7-LUT scan (gate-mode engines never need it).
+    const char* cap_env = std::getenv("SBOXGATES_HIT_CAP");
+    impl->hit_cap = cap_env != nullptr ? std::strtoull(cap_env, nullptr, 10)
+                                       : (1ULL << 24);
+    return std::unique_ptr<GpuEngine>(new GpuEngine(impl.release()));
+  } catch (const std::exception& ex) {
+    if (err != nullptr) *err = ex.what();
+    return nullptr;
+  }
+}
+
+GpuEngine::~GpuEngine() { delete impl_; }
+
+int GpuEngine::device() const { return impl_->device; }
+std::string GpuEngine::device_name() const { return impl_->name; }
+
+bool GpuEngine::scan4_service_active() {
+  Impl* im = impl_;
+  if (im->svc != nullptr) return true;
+  if (im->svc_broken || im->svc_tried) return false;
+  im->svc_tried = true;
+  const char* off = std::getenv("SBOXGATES_NO_SVC");
+  if (off != nullptr && off[0] != '\0' && off[0] != '0') {
+    im->svc_broken = true;
+    return false;
+  }
+  std::string err;
+  im->svc = ScanService::acquire(im->device, &err);
+  if (im->svc == nullptr) {
+    im->svc_broken = true;
+    return false;
+  }
+  return true;
+}
+
+ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
+  ScanResult out;
+  const i64 total = n_choose_k(rq.n, k == 4 ? 3 : k);
+  if (begin >= total) return out;
+  if (end > total) end = total;
+  if (begin >= end) return out;
+
+  Impl* im = impl_;
+  SBG_HIP_CHECK(hipSetDevice(im->device));
+
+  // Service only for small/medium ranges: its 64-WG grid is sized for the
+  // request/response round trip, not for multi-million-candidate scans —
+  // those go to the one-shot kernel with a work-sized grid.
+  if (k == 4 && end - begin <= (1 << 20) && scan4_service_active()) {
+    if (rq.matcher == nullptr) throw std::runtime_error("scan4 needs matcher");
+    try {
+      return im->svc->scan4(rq, begin, end);
+    } catch (const std::exception& e) {
+      // Service failure (residency/timeout): permanently fall back to the
+      // one-shot launch path for this engine.
+      std::fprintf(stderr, "sboxgates: scan service disabled: %s\n", e.what());
+      im->svc.reset();
+      im->svc_broken = true;
+    }
+  } else if (k != 4 && im->svc != nullptr) {
+    // Do not let an idle-resident service delay other kernels.
+    im->svc->park();
+  }
+
+  // Upload the pool (through pinned staging) and reset the control block.
+  std::memcpy(im->h_pool, rq.tables, sizeof(ttable) * rq.n);
+  SBG_HIP_CHECK(hipMemcpyAsync(im->d_pool, im->h_pool, sizeof(ttable) * rq.n,
+                               hipMemcpyHostToDevice, im->stream));
+  std::memset(im->h_ctl, 0, sizeof(DevCtl));
+
+  ScanArgs args;
+  args.pool = im->d_pool;
+  args.ctl = im->d_ctl;
+  args.hits = im->d_hits;
+  args.hit_cap = im->hit_cap;
+  args.matcher = im->d_matcher;
+  args.T1 = rq.target & rq.mask;
+  args.T0 = ~rq.target & rq.mask;
+  args.n = rq.n;
+  args.begin = begin;
+  args.end = end;
+  args.excl = rq.excl_low64;
+  args.seed = rq.seed;
+  args.count_all = rq.count_all ? 1 : 0;
+  args.slices7 = 1;
+
+  if (k == 3 || k == 4) {
+    if (k == 4) {
+      if (rq.matcher == nullptr) throw std::runtime_error("scan4 needs matcher");
+      if (im->last_matcher != rq.matcher) {
+        // The matcher is per-engine and immutable; upload once.
+        SBG_HIP_CHECK(hipMemcpy(im->d_matcher, rq.matcher, sizeof(Avail3Matcher),
+                                hipMemcpyHostToDevice));
+        im->last_matcher = rq.matcher;
+      }
+    }
+    i64 range = end - begin;
+    int grid = static_cast<int>(std::min<i64>((range + SCAN_BLOCK - 1) / SCAN_BLOCK,
+                                              4096));
+    im->run(k == 3 ? k_scan3 : k_scan4, grid, args);
+  } else if (k == 5) {
+    // Seed the triple queue at the triple containing `begin`.
+    i64 t_begin, t_last;
+    prefix_rank_span(rq.n, 5, 3, begin, end, &t_begin, &t_last);
+    im->h_ctl->queue = static_cast<unsigned long long>(t_begin);
+    // Size the grid to the triple count: small scans (deep recursion) pay
+    // for pool staging per block, so an always-2048 grid costs ~10x the
+    // useful work there.
+    i64 tcount = t_last - t_begin + 1;
+    int grid = static_cast<int>(std::min<i64>((tcount + TB - 1) / TB + 1, 2048));
+    im->run(k_scan5, grid, args);
+  } else if (k == 7) {
+    if (im->d_hits == nullptr) {
+      SBG_HIP_CHECK(hipMalloc(&im->d_hits, sizeof(Hit7) * im->hit_cap));
+      // args was built before the allocation; refresh the pointer.
+    }
+    args.hits = im->d_hits;
+    // Filter + assign, with overflow-driven range splitting.
+    i64 lo = begin;
+    while (lo < end) {
+      i64 hi = end;
+      for (;;) {
+        std::memset(im->h_ctl, 0, sizeof(DevCtl));
+        i64 q_begin, q_last;
+        prefix_rank_span(rq.n, 7, 4, lo, hi, &q_begin, &q_last);
+        i64 qcount = q_last - q_begin + 1;
+        // Sub-quad slicing: a single quad prefix can hold C(n-4,3) triples
+        // (tens of thousands); without slicing a small scan runs on a
+        // handful of blocks and leaves the chip idle.
+        i64 want_units = (hi - lo + SLICE_UNIT - 1) / SLICE_UNIT;
+        int slices = static_cast<int>(
+            std::clamp<i64>(want_units / std::max<i64>(qcount, 1), 1, 256));
+        ScanArgs a2 = args;
+        a2.begin = lo;
+        a2.end = hi;
+        a2.slices7 = slices;
+        im->h_ctl->queue = static_cast<unsigned long long>(q_begin * slices);
+        int grid7 = static_cast<int>(
+            std::min<i64>((qcount * slices + QB - 1) / QB + 1, 2048));
+        im->run(k_scan7_filter, grid7, a2);
+        if (im->h_ctl->overflow == 0) break;
+        // Too many feasible combinations for the buffer: halve the range.
+        hi = lo + (hi - lo) / 2;
+        if (hi <= lo + 1) {
+          throw std::runtime_error("7-LUT hit buffer too small for one combo");
+        }
+      }
+      // Accounting invariant: h_ctl is zeroed at the top of every attempt,
+      // so only the final (non-overflowed) attempt's counter lands here —
+      // combinations re-scanned after an overflow are never double-counted.
+      out.evaluated += im->h_ctl->evaluated;
+      unsigned long long nhits = im->h_ctl->hit_count;
+      if (nhits > im->hit_cap) nhits = im->hit_cap;
+      if (nhits > 0 && !rq.count_all) {
+        u64 items = nhits * LUT7_NUM_ORDERINGS * FM_SPLIT;
+        int grid = static_cast<int>(
+            std::min<u64>((items + SCAN_BLOCK - 1) / SCAN_BLOCK, 4096));
+        // h_ctl still holds the filter's final state, which the upload
+        // puts back unchanged.
+        im->run(k_scan7_assign, grid, im->d_hits, nhits, im->d_ctl, rq.seed);
+        if (im->h_ctl->found != 0) {
+          out.found = true;
+          std::memcpy(out.res, im->h_ctl->res, sizeof(out.res));
+          return out;
+        }
+      }
+      lo = hi;
+    }
+    return out;
+  } else {
+    throw std::runtime_error("GpuEngine::scan: bad k");
+  }
+
+  out.evaluated = im->h_ctl->evaluated;
+  if (im->h_ctl->found != 0) {
+    out.found = true;
+    std::memcpy(out.res, im->h_ctl->res, sizeof(out.res));
+  }
+  return out;
+}
+
+}  // namespace sbg

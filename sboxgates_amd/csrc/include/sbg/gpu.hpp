@@ -1,5 +1,7 @@
 // gpu.hpp — single-GPU scan engine: CDNA4 (gfx950) HIP kernels for the
-// 3/5/7-LUT candidate scans. Implementation: csrc/hip/kernels.hip.
+// 3/5/7-LUT candidate scans. Implementation: csrc/hip/scan_kernels.hip
+// (one-shot kernels, GpuEngine) and csrc/hip/scan_service.hip (persistent
+// k=4 service).
 //
 // One GpuEngine owns one device (HIP_VISIBLE_DEVICES / torchrun LOCAL_RANK
 // selects which): multi-GPU runs use one process per GPU with RCCL-backed

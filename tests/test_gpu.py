@@ -227,6 +227,117 @@ def test_scan4_gpu_matches_cpu(engines):
         assert tt_eq_mask(target, got, mask)
 
 
+def test_scan4_oneshot_kernel_matches_cpu(engines):
+    """Pool 186 is the smallest whose full triple range (C(186,3) =
+    1,055,240) exceeds the 2^20 cutoff of the persistent service, so this
+    scan runs on the one-shot k_scan4 kernel: counts + planted hits.
+    (`engines` only for its no-GPU skip; k=4 needs try_nots engines.)"""
+    from sboxgates_amd.ops import function_lists
+    pool = 186
+    gpu = make_engine(seed=1, gpu="force", save_states=False, try_nots=True)
+    cpu = make_engine(seed=1, gpu="off", save_states=False, try_nots=True)
+    sbox, n = models.load("rijndael")
+    gpu.set_sbox(sbox, n)
+    cpu.set_sbox(sbox, n)
+    st = gpu.initial_state()
+    st.grow_pool_random(pool, 0xFEED)
+    mask = mask_for_inputs(8)
+    total = n_choose_k(pool, 3)
+    assert total > 1 << 20
+    _, _, ev_g = gpu.scan_pool(4, st, gpu.target(0), mask, 0, total,
+                               count_all=True)
+    _, _, ev_c = cpu.scan_pool(4, st, cpu.target(0), mask, 0, total,
+                               count_all=True)
+    assert ev_g == ev_c == total
+    _, _, threes = function_lists(2 + 64 + 128, True)
+    rng = random.Random(3)
+    perms = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
+    for trial in range(3):
+        f = rng.choice(threes)
+        ids = sorted(rng.sample(range(pool), 3))
+        target = gen_lut_ttable(f["fun"], st.gate(ids[0])["table"],
+                                st.gate(ids[1])["table"], st.gate(ids[2])["table"])
+        found, res, _ = gpu.scan_pool(4, st, target, mask, 0, total)
+        assert found, trial
+        sel = perms[res[1]]
+        gids = [res[2], res[3], res[4]]
+        got = gen_lut_ttable(threes[res[0]]["fun"],
+                             st.gate(gids[sel[0]])["table"],
+                             st.gate(gids[sel[1]])["table"],
+                             st.gate(gids[sel[2]])["table"])
+        assert tt_eq_mask(target, got, mask)
+
+
+def test_scan7_filter_subquad_slicing(engines):
+    """Windows of a few thousand 7-combinations at pool 40 make the host
+    cut each quad's tail-triple window into 4, 2 or 1 slices; counts must
+    match the CPU for every factor, and a solution planted in a sliced
+    quad must still be found."""
+    gpu, cpu = engines
+    st = make_pool(gpu, 40, 0x51CE)
+    mask = mask_for_inputs(8)
+    q = n_choose_k(36, 3)
+    assert q == 7140
+    for a, b in [(0, q),                  # one quad, factor 4
+                 (100, 7000),             # inside one quad, factor 4
+                 (q - 3000, q + 6000),    # two quads, unequal parts, factor 2
+                 (q - 5, q + 5000)]:      # factor 1, straddles a quad boundary
+        _, _, ev_g = gpu.scan_pool(7, st, gpu.target(0), mask, a, b,
+                                   count_all=True)
+        _, _, ev_c = cpu.scan_pool(7, st, gpu.target(0), mask, a, b,
+                                   count_all=True)
+        assert ev_g == ev_c == b - a, (a, b, ev_g, ev_c)
+    # Quad (0,1,2,3) plus the tail triple of rank 83.
+    tabs = [st.gate(i)["table"] for i in [0, 1, 2, 3, 4, 7, 24]]
+    t_o = gen_lut_ttable(0x3C, tabs[0], tabs[1], tabs[2])
+    t_m = gen_lut_ttable(0xA5, tabs[3], tabs[4], tabs[5])
+    target = gen_lut_ttable(0x96, t_o, t_m, tabs[6])
+    f_c, _, _ = cpu.scan_pool(7, st, target, mask, 0, q, seed=5)
+    assert f_c
+    found, res, _ = gpu.scan_pool(7, st, target, mask, 0, q, seed=5)
+    assert found
+    g_o = gen_lut_ttable(res[0], st.gate(res[3])["table"],
+                         st.gate(res[4])["table"], st.gate(res[5])["table"])
+    g_m = gen_lut_ttable(res[1], st.gate(res[6])["table"],
+                         st.gate(res[7])["table"], st.gate(res[8])["table"])
+    got = gen_lut_ttable(res[2], g_o, g_m, st.gate(res[9])["table"])
+    assert tt_eq_mask(target, got, mask)
+
+
+def test_scan7_filter_exclusions(engines):
+    """k_scan7_filter under exclusion masks: an excluded prefix gate drops
+    the whole quad, an excluded tail gate drops single candidates; counts
+    must equal the CPU's for every (exclusion set, window)."""
+    gpu, cpu = engines
+    pool = 24
+    st = make_pool(gpu, pool, 0xE7C1)
+    mask = mask_for_inputs(8)
+    total = n_choose_k(pool, 7)
+    six = 0
+    for g in random.Random(11).sample(range(pool), 6):
+        six |= 1 << g
+    windows = [(0, total), (12345, 62345), (total - 3000, total)]
+    counts = {}
+    for excl in (1 << 0, 1 << 2, 1 << 20, 1 << 23, 0xff, six):
+        acted = False
+        for a, b in windows:
+            _, _, ev_g = gpu.scan_pool(7, st, gpu.target(0), mask, a, b,
+                                       count_all=True, excl=excl)
+            _, _, ev_c = cpu.scan_pool(7, st, gpu.target(0), mask, a, b,
+                                       count_all=True, excl=excl)
+            assert ev_g == ev_c, (hex(excl), a, b, ev_g, ev_c)
+            counts[excl, a] = ev_c
+            acted = acted or 0 < ev_c < b - a
+        assert acted, hex(excl)
+    # The CPU oracle itself, in closed form where one exists.
+    assert counts[1 << 0, 12345] == 0             # window inside gate 0's quads
+    assert counts[1 << 0, total - 3000] == 3000   # window past gate 0
+    assert counts[1 << 23, total - 3000] == 1436  # tail-only exclusion
+    for g in (0, 2, 20, 23):
+        assert counts[1 << g, 0] == n_choose_k(pool - 1, 7) == 245157
+    assert counts[0xff, 0] == n_choose_k(pool - 8, 7) == 11440
+
+
 def test_rijndael_gate_mode_bit0_gpu():
     """AES S-box output bit 0, 2-input {AND,OR,XOR} gate set, single GPU —
     BASELINE config 2's single-output core, with the step-4 triple scan on

@@ -64,7 +64,9 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan3(ScanArgs args) {
   const u64 local_eval = walk_triples(
       s_pool, args.n, args.T1, args.T0, args.count_all, ctl, idx0, args.end,
       stride, [&](i64 idx, int a, int b, int c, u32 p1, u32 p0) {
-        u8 func = lut3_function_from_p(p1, p0, scan_rnd(args.seed, idx));
+        // Same random word as cpu_scan3 (see scan_rnd in sbg/rng.hpp).
+        u8 func = lut3_function_from_p(
+            p1, p0, hash_mix64(args.seed ^ static_cast<u64>(idx)));
         if (args.count_all || func == 0) return false;
         u16 res[10] = {};
         res[0] = func;
@@ -695,6 +697,18 @@ struct GpuEngine::Impl {
   bool svc_broken = false;
 
   ~Impl() {
+    // hipFree waits for the whole device, a resident service kernel
+    // included: stop that kernel first, or the first hipFree below sits out
+    // the service's idle limit (measured: 1.77 s per engine destroyed).
+    // Other engines that share the service relaunch it on their next scan.
+    if (svc != nullptr) {
+      try {
+        svc->park();
+      } catch (const std::exception&) {
+        // The kernel then retires by itself at its idle limit.
+      }
+      svc.reset();
+    }
     if (d_pool != nullptr) (void)hipFree(d_pool);
     if (d_matcher != nullptr) (void)hipFree(d_matcher);
     if (d_ctl != nullptr) (void)hipFree(d_ctl);

@@ -69,9 +69,16 @@ SBG_HD inline u64 hash_mix64(u64 z) {
   return z ^ (z >> 31);
 }
 
-// Random word of the candidate with flat rank idx in a seeded scan. The
-// 5-LUT kernel and cpu_scan5 both take it from here, so a given (seed,
-// combination) yields the same decomposition on either engine.
+// Random word of the candidate with flat rank idx in a seeded scan. Which
+// scan draws which word (a given (seed, combination) yields the same result
+// on either engine wherever both engines use the same one):
+//  * 5-LUT: scan_rnd(seed, rank), in k_scan5 and cpu_scan5 alike.
+//  * 3-LUT: hash_mix64(seed ^ rank), in k_scan3 and cpu_scan3 alike.
+//  * 7-LUT: cpu_scan7 draws hash_mix64(seed ^ rank) once per combination;
+//    k_scan7_assign draws scan_rnd(seed, hit * orderings + ordering) per
+//    (hit, ordering), and its winner among orderings is a race anyway, so
+//    the two engines' 7-LUT results are each valid but not comparable.
+//  * k=4 draws none: the first fitting order and function win.
 SBG_HD inline u64 scan_rnd(u64 seed, u64 idx) {
   return hash_mix64(seed ^ (idx * 0x9E3779B97F4A7C15ULL));
 }

@@ -461,7 +461,11 @@ def test_gpu_window_fuzz_soak(engines):
     hit must verify under the mask. This is the GPU-path analog of the CPU
     fuzz soaks (round-1 soaks exercised only the CPU path)."""
     import struct
+    from sboxgates_amd.ops import function_lists
     gpu, cpu = engines
+    # k=4 results index the engines' own list: default gates, no NOTs.
+    _, _, threes = function_lists(2 + 64 + 128, False)
+    perms = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
     rng = random.Random(0xF022)
     for trial in range(60):
         k = rng.choice([3, 4, 5, 5, 7, 7])
@@ -493,8 +497,15 @@ def test_gpu_window_fuzz_soak(engines):
         f_g, r_g, _ = gpu.scan_pool(k, st, target, mask, a, b, seed=trial)
         f_c, _, _ = cpu.scan_pool(k, st, target, mask, a, b, seed=trial)
         assert f_g == f_c, (trial, k, pool, a, b)
-        if f_g and k in (3, 5, 7):
-            if k == 3:
+        if f_g:
+            if k == 4:
+                sel = perms[r_g[1]]
+                gids = [r_g[2], r_g[3], r_g[4]]
+                got = gen_lut_ttable(threes[r_g[0]]["fun"],
+                                     st.gate(gids[sel[0]])["table"],
+                                     st.gate(gids[sel[1]])["table"],
+                                     st.gate(gids[sel[2]])["table"])
+            elif k == 3:
                 got = gen_lut_ttable(r_g[0], st.gate(r_g[1])["table"],
                                      st.gate(r_g[2])["table"],
                                      st.gate(r_g[3])["table"])

@@ -114,6 +114,7 @@ PYBIND11_MODULE(_core, m) {
   // --- basics ---
   m.attr("MAX_GATES") = MAX_GATES;
   m.attr("NO_GATE") = static_cast<int>(NO_GATE);
+  m.attr("SCAN5_WIDE_MIN_ROW") = SCAN5_WIDE_MIN_ROW;
   m.def("gpu_available", &gpu_available);
   m.def("gpu_count", &gpu_count);
 

@@ -103,45 +103,25 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4(ScanArgs args) {
 // ---------------------------------------------------------------------------
 // K3 — 5-LUT scan. Workgroups dequeue triple prefixes; the 8 prefix cells
 // (masked with target-1/target-0) are computed cooperatively into LDS; each
-// thread then takes row segments — one d, a few consecutive e — hoists the
-// d side of the most balanced live cell, screens the e's against it,
-// sends what passes through the remaining live cells, and runs the
-// 2-coloring decomposition solver on survivors (replacing the reference's
-// 10 x 256-function brute force, lut.c:174-246).
+// thread then takes one row d and a run of e's, screens the e's against
+// the most balanced live cell, sends what passes through the remaining
+// live cells, and runs the 2-coloring decomposition solver on survivors
+// (replacing the reference's 10 x 256-function brute force,
+// lut.c:174-246). Short rows: 4 consecutive e per task, d side hoisted
+// into registers, e's tables read row by row. Long rows: 64 e per task,
+// taken a table position at a time from the gate-transposed pool.
 // ---------------------------------------------------------------------------
 
-// (a & b) | acc in one VALU instruction. Written out because the compiler
-// rebalances a plain C chain of these into v_and_b32 pairs feeding
-// v_or3_b32 (11 instructions per 8-dword reduction instead of 8) and keeps
-// vectorized copies of the loop-invariant operands.
-__device__ __forceinline__ u32 dev_and_or(u32 a, u32 b, u32 acc) {
-  u32 r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc));
-  return r;
-}
-
-// (a & ~b) | acc, likewise one instruction (gfx950's three-input bit op,
-// truth table 0xba), so ~te is never materialised.
-__device__ __forceinline__ u32 dev_andn_or(u32 a, u32 b, u32 acc) {
-  u32 r;
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba"
-      : "=v"(r) : "v"(a), "v"(b), "v"(acc));
-  return r;
-}
-
-// 16-byte LDS read of a pool row half (rows are u64 words at a 16 B
-// aligned stride; may_alias makes the differently-typed read well defined).
-typedef u32 lds_u32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
-
 // Survivor handling for k_scan5 (rare path; noinline keeps its registers
-// out of the hot loop's budget).
+// out of the hot loop's budget). STR: the pool's LDS stride.
+template <int STR>
 __device__ __attribute__((noinline)) void scan5_handle_survivor(
     const ScanArgs& args, DevCtl* ctl, const u64* s_pool, const u16* abc,
     i64 rank, int d, int e) {
   ttable tt5[5];
   const int ids[5] = {abc[0], abc[1], abc[2], d, e};
   for (int j = 0; j < 5; j++) {
-    for (int w = 0; w < 4; w++) tt5[j].w[w] = s_pool[ids[j] * PSTR + w];
+    for (int w = 0; w < 4; w++) tt5[j].w[w] = s_pool[ids[j] * STR + w];
   }
   u32 p1, p0;
   if (!lut5_p_masks(tt5, args.T1, args.T0, &p1, &p0)) return;
@@ -163,23 +143,87 @@ __device__ __attribute__((noinline)) void scan5_handle_survivor(
   dev_publish(ctl, res);
 }
 
+// The same test as the screen's on the remaining live cells of pair (d, e),
+// then the solver. Shared by both walks of k_scan5.
+template <int STR>
+__device__ __forceinline__ void scan5_after_screen(
+    const ScanArgs& args, DevCtl* ctl, const u64* s_pool,
+    const u64 (*H1)[4], const u64 (*H0)[4], const u16* abc, u32 other_live,
+    i64 rank, int d, int e) {
+  u64 td_[4], te_[4];
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    td_[w] = s_pool[d * STR + w];
+    te_[w] = s_pool[e * STR + w];
+  }
+  for (u32 lm = other_live; lm != 0; lm &= lm - 1) {
+    const int u = __ffs(lm) - 1;
+    u64 r11_1 = 0, r10_1 = 0, r01_1 = 0, r00_1 = 0;
+    u64 r11_0 = 0, r10_0 = 0, r01_0 = 0, r00_0 = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const u64 h1 = H1[u][w];
+      const u64 h0 = H0[u][w];
+      // x & ~y == x ^ (x & y): avoids materializing ~td/~te.
+      const u64 a1 = h1 & td_[w];
+      const u64 na1 = h1 ^ a1;
+      const u64 a0 = h0 & td_[w];
+      const u64 na0 = h0 ^ a0;
+      const u64 x11_1 = a1 & te_[w];
+      const u64 x01_1 = na1 & te_[w];
+      const u64 x11_0 = a0 & te_[w];
+      const u64 x01_0 = na0 & te_[w];
+      r11_1 |= x11_1;
+      r10_1 |= a1 ^ x11_1;
+      r01_1 |= x01_1;
+      r00_1 |= na1 ^ x01_1;
+      r11_0 |= x11_0;
+      r10_0 |= a0 ^ x11_0;
+      r01_0 |= x01_0;
+      r00_0 |= na0 ^ x01_0;
+    }
+    if ((r11_1 && r11_0) || (r10_1 && r10_0) || (r01_1 && r01_0) ||
+        (r00_1 && r00_0)) {
+      return;
+    }
+  }
+  scan5_handle_survivor<STR>(args, ctl, s_pool, abc, rank, d, e);
+}
+
+// WIDE: the variant for pools with rows longer than SCAN5_WIDE_MIN_ROW. It
+// keeps the gate-transposed pool in LDS next to the row-form pool (at the
+// dense stride, to stay within a quarter of a CU's LDS) and sends every
+// batch with such a row through the wide walk. The host picks the variant
+// by pool size, so pools without long rows run the 48 B-stride kernel
+// with no transposed pool to build.
+template <bool WIDE>
 __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   // Triple batching: one dequeue + one cooperative prefix-cell build + one
   // barrier per TB triples (measured at TB=1: 48% of wave time parked on
   // the per-triple barriers; batching amortizes them 8x).
   //
-  // The row screen reads whole segments of up to SEG_MAX pool rows without
+  // The short-row screen reads whole segments of SEG pool rows without
   // per-pair bounds tests; the pad rows keep a segment that starts at the
   // pool's last gate inside the array (their content is masked out).
-  constexpr int SEG_MAX = 16;
-  __shared__ alignas(16) u64 s_pool[(MAX_GATES + SEG_MAX) * PSTR];
+  constexpr int STR = WIDE ? PSTR_DENSE : PSTR;
+  constexpr int SEG = 4, LG_SEG = 2;
+  // Wide walk: a task screens the 32 NW gates of NW aligned words of G.
+  constexpr int NW = SCAN5_WIDE_WORDS;
+  constexpr int GB = 32 * NW;
+  __shared__ alignas(16) u64 s_pool[(MAX_GATES + SEG) * STR];
+  __shared__ alignas(16) u32 s_G[WIDE ? GT_DWORDS : 1];
+  __shared__ int s_cnt[TB];      // wide walk: tasks per triple, unpadded
+  __shared__ int s_wide;         // this batch takes the wide walk
+  // Wide walk: position lists of each triple's screen cell (see
+  // gt_build_lists), their padded lengths and the target-0 list's offset.
+  __shared__ alignas(16) u8 s_pos[WIDE ? TB : 1][GT_LIST_BYTES];
+  __shared__ int s_npos[TB][3];
   __shared__ alignas(16) u64 s_H1[TB][8][4];
   __shared__ alignas(16) u64 s_H0[TB][8][4];
   __shared__ i64 s_base[TB];     // flat-rank base of each triple
   __shared__ i64 s_lo[TB], s_prefix[TB + 1];
   __shared__ int s_hi[TB];       // window end (flat pair index) per triple
-  __shared__ int s_tpre[TB + 1]; // prefix sums of row-segment task counts
-  __shared__ int s_seg;          // segment length of this batch
+  __shared__ int s_tpre[TB + 1]; // prefix sums of the walk's task counts
   __shared__ int s_m[TB];
   __shared__ u16 s_abc[TB][3];
   __shared__ u32 s_live[TB];     // cells with both forced-1 and forced-0
@@ -190,7 +234,12 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   __shared__ int s_stop;         // all triples past range end
 
   const int n = args.n;
-  load_pool_lds(s_pool, args.pool, n);
+  load_pool_lds<STR>(s_pool, args.pool, n);
+  if constexpr (WIDE) {
+    __syncthreads();
+    // Published by the barriers of the first dequeue.
+    build_gate_transposed_lds<STR>(s_G, s_pool, n);
+  }
 
   DevCtl* ctl = args.ctl;
   const i64 total3 = cf3(n);
@@ -224,27 +273,43 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       // Row-segment tasks. A task is (triple, row d2, segment): the pairs
       // (d2, e2) with gap e2 - d2 - 1 in [s0, s0 + L). Segment s0 exists for
       // the rows d2 < m - 1 - s0, so a triple has sum_s (m - 1 - s * L)
-      // tasks. L follows the batch's longest row. Long rows get SEG_MAX:
-      // measured at pool 450, 16-pair segments beat 32-pair ones by 2.6%
-      // (half the ragged-tail waste for twice the d-side hoists). Short
-      // rows (the search's small pools) get 4 pairs, the flat walk's old
-      // run length: those scans are dominated by survivors going through
-      // the solver one after another in their lane, and 8-pair segments
-      // made the AES bit-0 search 15% slower than 4-pair ones.
+      // tasks. L = SEG = 4 pairs, the flat walk's old run length: the
+      // scans of the search's small pools are dominated by survivors going
+      // through the solver one after another in their lane, and 8-pair
+      // segments made the AES bit-0 search 15% slower than 4-pair ones.
+      //
+      // A batch whose longest row exceeds SCAN5_WIDE_MIN_ROW takes the wide
+      // walk instead. A task there is (triple, row d, word group Wg): the
+      // pairs (d, e) with e among the GB gates [GB Wg, GB Wg + GB), aligned
+      // to absolute gate ids so that G indexes directly. Group Wg has the
+      // rows c < d <= min(n - 2, GB Wg + GB - 2); only the last group,
+      // (n - 1) / GB, is cut by n - 2 and has all m - 1 rows. Each
+      // triple's task count is padded to a multiple of 64 so that a wave
+      // never holds two triples and the walk's position loop is scalar.
       int mmax = 0;
       for (int t = 0; t < TB; t++) {
         if (s_prefix[t + 1] != 0 && s_m[t] > mmax) mmax = s_m[t];
       }
-      const int lg = mmax > 40 ? 4 : 2;
-      const int L = 1 << lg;  // SEG_MAX at most
-      s_seg = L;
+      const bool wide = WIDE && mmax > SCAN5_WIDE_MIN_ROW;
+      s_wide = wide ? 1 : 0;
       s_tpre[0] = 0;
       for (int t = 0; t < TB; t++) {
         int cnt = 0;
         if (s_prefix[t + 1] != 0) {
           const int rows = s_m[t] - 1;
-          const int ns = (rows + L - 1) >> lg;
-          cnt = ns * rows - L * (ns * (ns - 1) / 2);
+          if (wide) {
+            const int c = n - 1 - s_m[t];
+            const int w_min = (c + 2) / GB, w_max = (n - 1) / GB;
+            const int k = w_max - w_min;  // groups not cut by n - 2
+            cnt = rows + k * (GB - 2 - c) + GB * (k * (w_min + w_max - 1) / 2);
+            s_cnt[t] = cnt;
+            cnt = (cnt + 63) & ~63;
+          } else {
+            const int ns = (rows + SEG - 1) >> LG_SEG;
+            cnt = ns * rows - SEG * (ns * (ns - 1) / 2);
+          }
+        } else if (wide) {
+          s_cnt[t] = 0;
         }
         s_tpre[t + 1] = s_tpre[t] + cnt;
       }
@@ -255,7 +320,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
     const i64 total_pairs = s_prefix[TB];
     if (total_pairs == 0) continue;
 
-    build_prefix_cells<3, TB>(s_pool, s_abc, s_prefix, args.T1, args.T0, s_H1,
+    build_prefix_cells<3, TB, STR>(s_pool, s_abc, s_prefix, args.T1, args.T0, s_H1,
                               s_H0);
     if (threadIdx.x < TB) s_best[threadIdx.x] = 0;
     if (mark_live_cells<3, TB>(s_H1, s_H0, s_live)) {
@@ -273,14 +338,111 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
                                 static_cast<u32>(7 - u));
     }
     __syncthreads();
+    if (WIDE && s_wide) {
+      // 32 threads per triple list the positions of its screen cell.
+      static_assert(SCAN_BLOCK == 32 * TB);
+      const int t = threadIdx.x >> 5;
+      if (s_prefix[t + 1] != s_prefix[t]) {  // else: cells not built
+        const int u0 = 7 - static_cast<int>(s_best[t] & 7u);
+        gt_build_lists(s_H1[t][u0], s_H0[t][u0], s_pos[t], s_npos[t],
+                       threadIdx.x & 31);
+      }
+      __syncthreads();
+    }
+
+    const int total_tasks = s_tpre[TB];
+    int since_poll = 0;
+
+    // Wide walk. Consecutive lanes take consecutive rows d of one word
+    // group, last group first (it has the most rows, so the per-lane search
+    // for the group is short). A wave holds one triple and mostly one
+    // group: its lanes read the same G dwords (LDS broadcast), and each
+    // brings its own td.
+    if (WIDE && s_wide) {
+      for (int task = threadIdx.x; task < total_tasks; task += blockDim.x) {
+        if (!args.count_all) {
+          since_poll += GB;
+          if (since_poll >= 64) {
+            since_poll = 0;
+            if (dev_abort(ctl)) break;
+          }
+        }
+        int t = 0;
+        while (s_tpre[t + 1] <= task) t++;
+        // Task counts are padded to the wave size: one triple per wave.
+        t = __builtin_amdgcn_readfirstlane(t);
+        int d2 = task - s_tpre[t];
+        if (d2 >= s_cnt[t]) continue;
+        const int m = s_m[t];
+        const int c = n - 1 - m;
+        int wg = (n - 1) / GB;
+        for (int rows = m - 1; d2 >= rows; rows = GB * wg + GB - 2 - c) {
+          d2 -= rows;
+          wg--;
+        }
+        const int d = c + 1 + d2;
+        const int e0 = GB * wg;  // gate of bit 0
+        // Flat pair index of bit 0 (negative where e0 <= d): bit i is the
+        // pair (d, e0 + i). Clip bits to e > d, to the pool's end and to
+        // the triple's [lo, hi) window.
+        const int q0 = d2 * m - d2 * (d2 + 1) / 2 + e0 - d - 1;
+        int i_lo = d + 1 - e0;
+        if (i_lo < 0) i_lo = 0;
+        const int lo = static_cast<int>(s_lo[t]);
+        if (i_lo < lo - q0) i_lo = lo - q0;
+        int i_hi = n - e0;
+        if (i_hi > GB) i_hi = GB;
+        if (i_hi > s_hi[t] - q0) i_hi = s_hi[t] - q0;
+        if (i_lo >= i_hi) continue;
+        u64 valid = (~0ULL >> (64 - i_hi)) & (~0ULL << i_lo);  // 1 <= i_hi
+        if (args.excl != 0) {
+          // An excluded d drops the whole row; excluded e's (ids < 64 only)
+          // drop out of the mask with one shift per task.
+          if (dev_excluded(args.excl, d)) continue;
+          if (e0 < 64) valid &= ~(args.excl >> e0);
+        }
+        local_eval += __popcll(valid);
+
+        // Screen: the listed positions of the screen cell. Per position
+        // the lanes read G at their candidate words (the same address
+        // across most of a wave: LDS broadcast) and at d's own word for
+        // td's bit. A cell that is not live has one side empty and rejects
+        // nothing, as in the short walk.
+        const u32 live = s_live[t];
+        const int u0 = 7 - static_cast<int>(s_best[t] & 7u);
+        const int n1 = __builtin_amdgcn_readfirstlane(s_npos[t][0]);
+        const int n0 = __builtin_amdgcn_readfirstlane(s_npos[t][1]);
+        GtWords<NW> vw;
+#pragma unroll
+        for (int k = 0; k < NW; k++) {
+          vw.w[k] = static_cast<u32>(valid >> (32 * k));
+        }
+        const GtWords<NW> pw =
+            gt_screen<NW>(s_pos[t], n1, s_pos[t] + s_npos[t][2], n0,
+                          &s_G[NW * wg], &s_G[d >> 5], d & 31, vw);
+        u64 pend = 0;
+#pragma unroll
+        for (int k = 0; k < NW; k++) {
+          pend |= static_cast<u64>(pw.w[k]) << (32 * k);
+        }
+
+        // Rare path. The screen only ever passes too much.
+        while (pend != 0) {
+          const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
+          pend &= pend - 1;
+          scan5_after_screen<STR>(args, ctl, s_pool, s_H1[t], s_H0[t],
+                                  s_abc[t], live & ~(1u << u0),
+                                  s_base[t] + q0 + i, d, e0 + i);
+        }
+      }
+      continue;
+    }
 
     // Row-segment walk. Consecutive lanes take consecutive rows d2 of one
     // segment column: a wave mostly shares t (same-address reads of the
     // prefix cells) and its lanes read consecutive pool rows, which the
     // 48 B stride keeps conflict-free.
-    const int L = __builtin_amdgcn_readfirstlane(s_seg);
-    const int total_tasks = s_tpre[TB];
-    int since_poll = 0;
+    constexpr int L = SEG;
     for (int task = threadIdx.x; task < total_tasks; task += blockDim.x) {
       if (!args.count_all) {
         // Abort poll once per 64 pairs walked, as the flat walk did.
@@ -309,7 +471,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       if (i_hi > L) i_hi = L;
       if (i_hi > s_hi[t] - q_seg) i_hi = s_hi[t] - q_seg;
       if (i_lo >= i_hi) continue;
-      u32 valid = ((1u << i_hi) - 1u) & ~((1u << i_lo) - 1u);  // i_hi <= 16
+      u32 valid = ((1u << i_hi) - 1u) & ~((1u << i_lo) - 1u);  // i_hi <= SEG
       // c + 1 + d2 with c = n - 1 - m (measured: fetching c from s_abc
       // here, one more LDS read per task, cost 1% on the bench).
       const int d = n - m + d2;
@@ -332,7 +494,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       u32 A1[8], A0[8], N1[8], N0[8];
 #pragma unroll
       for (int w = 0; w < 4; w++) {
-        const u64 tdw = s_pool[d * PSTR + w];
+        const u64 tdw = s_pool[d * STR + w];
         const u64 h1 = s_H1[t][u0][w], h0 = s_H0[t][u0][w];
         const u64 a1 = h1 & tdw, a0 = h0 & tdw;
         const u64 n1 = h1 ^ a1, n0 = h0 ^ a0;
@@ -346,101 +508,52 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
         N0[2 * w + 1] = static_cast<u32>(n0 >> 32);
       }
 
-      // e side: 8 positions per step, one bit per position whose cell u0
-      // has no quadrant holding both forced-1 and forced-0 content. All
-      // four quadrants are tested without a branch: on the benchmark pool
-      // a single quadrant rejects only ~40% of the candidates (the four
-      // together ~99%), so a wave almost never agrees on an early exit.
-      // No exclusion and no clipping per pair; reads past the row's end
-      // are masked by `valid`.
+      // e side: one bit per position whose cell u0 has no quadrant holding
+      // both forced-1 and forced-0 content. All four quadrants are tested
+      // without a branch: on the benchmark pool a single quadrant rejects
+      // only ~40% of the candidates (the four together ~99%), so a wave
+      // almost never agrees on an early exit. No exclusion and no clipping
+      // per pair; reads past the row's end are masked by `valid`.
       u32 pend = 0;
-      const u64* pe = &s_pool[e_first * PSTR];
-#pragma unroll 1
-      for (int base = 0; base < L; base += 8) {
-        if (((valid >> base) & 0xffu) == 0) continue;
-        u32 bits = 0;
+      const u64* pe = &s_pool[e_first * STR];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          // Pool rows start 16 B aligned (48 B stride): two ds_read_b128.
-          const lds_u32x4* p =
-              reinterpret_cast<const lds_u32x4*>(pe + (base + j) * PSTR);
-          const lds_u32x4 lo4 = p[0], hi4 = p[1];
-          const u32 te[8] = {lo4.x, lo4.y, lo4.z, lo4.w,
-                             hi4.x, hi4.y, hi4.z, hi4.w};
-          u32 x11_1 = A1[0] & te[0], x11_0 = A0[0] & te[0];
-          u32 x01_1 = N1[0] & te[0], x01_0 = N0[0] & te[0];
-          u32 x10_1 = A1[0] & ~te[0], x10_0 = A0[0] & ~te[0];
-          u32 x00_1 = N1[0] & ~te[0], x00_0 = N0[0] & ~te[0];
+      for (int j = 0; j < SEG; j++) {
+        // Pool rows start 16 B aligned: two ds_read_b128.
+        const lds_u32x4* p =
+            reinterpret_cast<const lds_u32x4*>(pe + j * STR);
+        const lds_u32x4 lo4 = p[0], hi4 = p[1];
+        const u32 te[8] = {lo4.x, lo4.y, lo4.z, lo4.w,
+                           hi4.x, hi4.y, hi4.z, hi4.w};
+        u32 x11_1 = A1[0] & te[0], x11_0 = A0[0] & te[0];
+        u32 x01_1 = N1[0] & te[0], x01_0 = N0[0] & te[0];
+        u32 x10_1 = A1[0] & ~te[0], x10_0 = A0[0] & ~te[0];
+        u32 x00_1 = N1[0] & ~te[0], x00_0 = N0[0] & ~te[0];
 #pragma unroll
-          for (int k = 1; k < 8; k++) {
-            x11_1 = dev_and_or(A1[k], te[k], x11_1);
-            x11_0 = dev_and_or(A0[k], te[k], x11_0);
-            x01_1 = dev_and_or(N1[k], te[k], x01_1);
-            x01_0 = dev_and_or(N0[k], te[k], x01_0);
-            x10_1 = dev_andn_or(A1[k], te[k], x10_1);
-            x10_0 = dev_andn_or(A0[k], te[k], x10_0);
-            x00_1 = dev_andn_or(N1[k], te[k], x00_1);
-            x00_0 = dev_andn_or(N0[k], te[k], x00_0);
-          }
-          // min(a, b) != 0 <=> both sides non-empty; kept arithmetic so
-          // the four tests do not turn into divergent branches.
-          const u32 conflict = min(x11_1, x11_0) | min(x10_1, x10_0) |
-                               min(x01_1, x01_0) | min(x00_1, x00_0);
-          bits |= static_cast<u32>(conflict == 0) << j;
+        for (int k = 1; k < 8; k++) {
+          x11_1 = dev_and_or(A1[k], te[k], x11_1);
+          x11_0 = dev_and_or(A0[k], te[k], x11_0);
+          x01_1 = dev_and_or(N1[k], te[k], x01_1);
+          x01_0 = dev_and_or(N0[k], te[k], x01_0);
+          x10_1 = dev_andn_or(A1[k], te[k], x10_1);
+          x10_0 = dev_andn_or(A0[k], te[k], x10_0);
+          x00_1 = dev_andn_or(N1[k], te[k], x00_1);
+          x00_0 = dev_andn_or(N0[k], te[k], x00_0);
         }
-        pend |= bits << base;
+        // min(a, b) != 0 <=> both sides non-empty; kept arithmetic so
+        // the four tests do not turn into divergent branches.
+        const u32 conflict = min(x11_1, x11_0) | min(x10_1, x10_0) |
+                             min(x01_1, x01_0) | min(x00_1, x00_0);
+        pend |= static_cast<u32>(conflict == 0) << j;
       }
       pend &= valid;
 
-      // Rare path: the same test on the remaining live cells, then the
-      // solver. The screen only ever passes too much.
+      // Rare path. The screen only ever passes too much.
       while (pend != 0) {
         const int i = __ffs(pend) - 1;
         pend &= pend - 1;
-        const int e = e_first + i;
-        u64 td_[4], te_[4];
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-          td_[w] = s_pool[d * PSTR + w];
-          te_[w] = s_pool[e * PSTR + w];
-        }
-        bool ok = true;
-        for (u32 lm = live & ~(1u << u0); lm != 0; lm &= lm - 1) {
-          const int u = __ffs(lm) - 1;
-          u64 r11_1 = 0, r10_1 = 0, r01_1 = 0, r00_1 = 0;
-          u64 r11_0 = 0, r10_0 = 0, r01_0 = 0, r00_0 = 0;
-#pragma unroll
-          for (int w = 0; w < 4; w++) {
-            const u64 h1 = s_H1[t][u][w];
-            const u64 h0 = s_H0[t][u][w];
-            // x & ~y == x ^ (x & y): avoids materializing ~td/~te.
-            const u64 a1 = h1 & td_[w];
-            const u64 na1 = h1 ^ a1;
-            const u64 a0 = h0 & td_[w];
-            const u64 na0 = h0 ^ a0;
-            const u64 x11_1 = a1 & te_[w];
-            const u64 x01_1 = na1 & te_[w];
-            const u64 x11_0 = a0 & te_[w];
-            const u64 x01_0 = na0 & te_[w];
-            r11_1 |= x11_1;
-            r10_1 |= a1 ^ x11_1;
-            r01_1 |= x01_1;
-            r00_1 |= na1 ^ x01_1;
-            r11_0 |= x11_0;
-            r10_0 |= a0 ^ x11_0;
-            r01_0 |= x01_0;
-            r00_0 |= na0 ^ x01_0;
-          }
-          if ((r11_1 && r11_0) || (r10_1 && r10_0) || (r01_1 && r01_0) ||
-              (r00_1 && r00_0)) {
-            ok = false;
-            break;
-          }
-        }
-        if (ok) {
-          scan5_handle_survivor(args, ctl, s_pool, s_abc[t],
-                                s_base[t] + q_seg + i, d, e);
-        }
+        scan5_after_screen<STR>(args, ctl, s_pool, s_H1[t], s_H0[t], s_abc[t],
+                                live & ~(1u << u0), s_base[t] + q_seg + i, d,
+                                e_first + i);
       }
     }
   }
@@ -889,7 +1002,13 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
     // useful work there.
     i64 tcount = t_last - t_begin + 1;
     int grid = static_cast<int>(std::min<i64>((tcount + TB - 1) / TB + 1, 2048));
-    im->run(k_scan5, grid, args);
+    // Pools without a row longer than the crossover never take the wide
+    // walk: they get the variant that has no transposed pool to build.
+    if (rq.n - 3 > SCAN5_WIDE_MIN_ROW) {
+      im->run(k_scan5<true>, grid, args);
+    } else {
+      im->run(k_scan5<false>, grid, args);
+    }
   } else if (k == 7) {
     if (im->d_hits == nullptr) {
       SBG_HIP_CHECK(hipMalloc(&im->d_hits, sizeof(Hit7) * im->hit_cap));

@@ -15,6 +15,15 @@
 
 namespace sbg {
 
+// 5-LUT scan: a batch of triples whose longest row (the gates behind the
+// triple's last one, m = n - 1 - c) exceeds this takes the wide walk, which
+// screens the e's of a row one 32-gate word of the gate-transposed pool at a
+// time; shorter rows keep the 4-pair row segments. Pools of at most
+// SCAN5_WIDE_MIN_ROW + 3 gates therefore never reach the wide walk.
+constexpr int SCAN5_WIDE_MIN_ROW = 40;
+// 32-gate words of the transposed pool per wide task (1 or 2).
+constexpr int SCAN5_WIDE_WORDS = 2;
+
 class GpuEngine {
  public:
   // Returns nullptr when no HIP device is visible (err describes why).

@@ -21,6 +21,7 @@
 #include "sbg/rng.hpp"
 #include "sbg/sboxio.hpp"
 #include "sbg/scan.hpp"
+#include "sbg/scan5_geom.hpp"
 #include "sbg/search.hpp"
 #include "sbg/state.hpp"
 #include "sbg/xmlio.hpp"
@@ -172,6 +173,28 @@ PYBIND11_MODULE(_core, m) {
     decode_pair(q, m, &d, &e);
     return py::make_tuple(d, e);
   });
+
+  // --- k_scan5 wide-walk geometry (sbg/scan5_geom.hpp, shared with the
+  // kernel) ---
+  m.attr("SCAN5_WIDE_GB") = SCAN5_WIDE_GB;
+  m.def("scan5_wide_pad", &scan5_wide_pad);
+  // Tasks of the triple whose last gate is c, window [lo, hi) of flat pair
+  // indices: (d, real id of the gate on bit 0, valid mask) per task, in
+  // task order.
+  m.def("scan5_wide_tasks", [](int n, int c, int lo, int hi, u64 excl) {
+    if (n < 3 || n > MAX_GATES || c < 0 || c > n - 3) {
+      throw std::invalid_argument("scan5_wide_tasks: need 0 <= c <= n - 3");
+    }
+    const int pad = scan5_wide_pad(n);
+    const int count = scan5_wide_task_count(n, pad, c);
+    py::list out;
+    for (int task = 0; task < count; task++) {
+      const Scan5WideTask t = scan5_wide_decode(n, pad, c, task);
+      out.append(py::make_tuple(t.d, t.e0, scan5_wide_valid(t, lo, hi, excl)));
+    }
+    return out;
+  }, py::arg("n"), py::arg("c"), py::arg("lo"), py::arg("hi"),
+     py::arg("excl") = 0);
 
   // --- lutcover primitives (for oracle tests) ---
   m.def("naive_check_n_lut_possible",

@@ -229,7 +229,10 @@ __device__ __forceinline__ void load_pool_lds(u64* s_pool, const ttable* pool,
 
 // ---------------------------------------------------------------------------
 // Gate-transposed pool. G[p][W], p a truth-table position and W a 32-gate
-// word: bit i of G[p][W] is bit p of gate 32 W + i (0 for gates >= n). One
+// word: bit i of G[p][W] is bit p of the gate with shifted id 32 W + i,
+// i.e. of gate 32 W + i - pad (0 where that is no gate of the pool). The
+// caller chooses pad so that the pool's last gate ends a word group (see
+// sbg/scan5_geom.hpp); n + pad <= 32 GT_WORDS. One
 // dword then holds one table position of 32 candidates' last gate, and a
 // cell test over those candidates costs a few instructions per position of
 // the cell instead of a pass over whole 256-bit tables per candidate.
@@ -251,15 +254,15 @@ typedef u32 lds_u32 __attribute__((may_alias));
 template <int STR>
 __device__ __forceinline__ void build_gate_transposed_lds(u32* s_G,
                                                           const u64* s_pool,
-                                                          int n) {
+                                                          int n, int pad) {
   const int lane = threadIdx.x & 63;
   const int nwaves = blockDim.x >> 6;
-  const int items = ((n + 63) >> 6) * 8;  // (64-gate chunk, table word)
+  const int items = ((n + pad + 63) >> 6) * 8;  // (64-id chunk, table word)
   for (int item = threadIdx.x >> 6; item < items; item += nwaves) {
     const int chunk = item >> 3, w = item & 7;
-    const int gate = chunk * 64 + lane;
+    const int gate = chunk * 64 + lane - pad;
     u32 row = 0;
-    if (gate < n) {
+    if (gate >= 0 && gate < n) {
       row = reinterpret_cast<const lds_u32*>(&s_pool[gate * STR])[w];
     }
     u32 lo = 0, hi = 0;
@@ -277,6 +280,12 @@ __device__ __forceinline__ void build_gate_transposed_lds(u32* s_G,
       dst[1] = hi;
     }
   }
+}
+
+// A value that every lane of the wave holds alike, as a scalar.
+__device__ __forceinline__ u32 dev_uniform(u32 v) {
+  return static_cast<u32>(
+      __builtin_amdgcn_readfirstlane(static_cast<int>(v)));
 }
 
 // G[p][W .. W + NW) for NW in {1, 2}, W even when NW == 2; gw = &G[0][W].
@@ -352,17 +361,22 @@ __device__ __forceinline__ void gt_accumulate(GtSide<NW>& s,
 // side's positions in ascending order as bytes, padded to a multiple of
 // GT_LIST_STEP by repeating the last one (accumulating a position twice
 // changes nothing). The target-1 list starts at byte 0, the target-0 list
-// at the next multiple of 16; both are read 16 bytes at a time.
+// at the next multiple of 16; both are read 16 bytes at a time. The first
+// GT_HEAD_BYTES of each list are filed a second time, side by side (target-1
+// at byte 0, target-0 at byte GT_HEAD_BYTES of `head`), for a reader that
+// wants them next to its other per-cell data; bytes past a list's padded
+// length are left as they were.
 constexpr int GT_LIST_STEP = 4;
 constexpr int GT_LIST_BYTES = 256 + 2 * 16;
+constexpr int GT_HEAD_BYTES = 16;
 
 // Called by 32 threads, part = 0..31, each filing the 8 positions of byte
 // `part` of the cell's forced sets (h1, h0: 4 words each, disjoint).
 // counts[0], counts[1]: the lists' padded lengths; counts[2]: the target-0
 // list's byte offset.
 __device__ __forceinline__ void gt_build_lists(const u64* h1, const u64* h0,
-                                               u8* list, int* counts,
-                                               int part) {
+                                               u8* list, u8* head,
+                                               int* counts, int part) {
   const int wd = part >> 3, sh = (part & 7) * 8;
   int base = 0;
   for (int side = 0; side < 2; side++) {
@@ -381,10 +395,18 @@ __device__ __forceinline__ void gt_build_lists(const u64* h1, const u64* h0,
       int p = 0;
       for (; mine != 0; mine &= mine - 1) {
         p = part * 8 + __ffs(mine) - 1;
+        if (at < GT_HEAD_BYTES) {
+          head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
+        }
         list[base + at++] = static_cast<u8>(p);
       }
       if (at == total) {  // the side's last position is here: pad with it
-        for (; at < padded; at++) list[base + at] = static_cast<u8>(p);
+        for (; at < padded; at++) {
+          if (at < GT_HEAD_BYTES) {
+            head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
+          }
+          list[base + at] = static_cast<u8>(p);
+        }
       }
     }
     if (part == 0) counts[side] = padded;
@@ -431,14 +453,19 @@ __device__ __forceinline__ void gt_accumulate_step(GtSide<NW>& s, u32 pw,
 // the first 8 and none the first 12, against 104 positions in the cell), so
 // the cost follows that number and not the cell's size. The list bytes go through
 // SGPRs; only the G reads, the bit extract and the accumulation are
-// vector work. Call from code that the whole wave runs together.
+// vector work. head1, head0: the lists' first GT_HEAD_BYTES, already in
+// scalars (gt_build_lists' `head`), so that the first G reads wait for no
+// list read. Call from code that the whole wave runs together.
 template <int NW>
-__device__ __forceinline__ GtWords<NW> gt_screen(const u8* list1, int n1,
+__device__ __forceinline__ GtWords<NW> gt_screen(const u32 (&head1)[4],
+                                                 const u32 (&head0)[4],
+                                                 const u8* list1, int n1,
                                                  const u8* list0, int n0,
                                                  const u32* gw, const u32* gx,
                                                  u32 xbit,
                                                  const GtWords<NW>& valid) {
   static_assert(GT_LIST_STEP == 4);  // one dword of list bytes per step
+  static_assert(GT_HEAD_BYTES == 16);  // one pass of the loop below
   GtWords<NW> pend = valid;
   // An empty side cannot contradict: everything passes.
   if (n1 == 0 || n0 == 0) return pend;
@@ -455,19 +482,27 @@ __device__ __forceinline__ GtWords<NW> gt_screen(const u8* list1, int n1,
   };
   for (int k = 0; k < nmax; k += 16) {
     u32 pw1[4] = {}, pw0[4] = {};
-    if (k < n1) {
-      const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list1 + k);
-      pw1[0] = __builtin_amdgcn_readfirstlane(v.x);
-      pw1[1] = __builtin_amdgcn_readfirstlane(v.y);
-      pw1[2] = __builtin_amdgcn_readfirstlane(v.z);
-      pw1[3] = __builtin_amdgcn_readfirstlane(v.w);
-    }
-    if (k < n0) {
-      const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list0 + k);
-      pw0[0] = __builtin_amdgcn_readfirstlane(v.x);
-      pw0[1] = __builtin_amdgcn_readfirstlane(v.y);
-      pw0[2] = __builtin_amdgcn_readfirstlane(v.z);
-      pw0[3] = __builtin_amdgcn_readfirstlane(v.w);
+    if (k == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        pw1[j] = head1[j];
+        pw0[j] = head0[j];
+      }
+    } else {
+      if (k < n1) {
+        const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list1 + k);
+        pw1[0] = __builtin_amdgcn_readfirstlane(v.x);
+        pw1[1] = __builtin_amdgcn_readfirstlane(v.y);
+        pw1[2] = __builtin_amdgcn_readfirstlane(v.z);
+        pw1[3] = __builtin_amdgcn_readfirstlane(v.w);
+      }
+      if (k < n0) {
+        const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list0 + k);
+        pw0[0] = __builtin_amdgcn_readfirstlane(v.x);
+        pw0[1] = __builtin_amdgcn_readfirstlane(v.y);
+        pw0[2] = __builtin_amdgcn_readfirstlane(v.z);
+        pw0[3] = __builtin_amdgcn_readfirstlane(v.w);
+      }
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {

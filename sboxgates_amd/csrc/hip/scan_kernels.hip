@@ -31,6 +31,7 @@
 #include <string>
 
 #include "sbg/comb.hpp"
+#include "sbg/scan5_geom.hpp"
 #include "scan_device.hpp"
 #include "scan_service.hpp"
 
@@ -190,6 +191,118 @@ __device__ __forceinline__ void scan5_after_screen(
   scan5_handle_survivor<STR>(args, ctl, s_pool, abc, rank, d, e);
 }
 
+// LDS pointers, for k_scan5's arrays as arguments of its wide walk (a plain
+// pointer argument would turn every read into a flat access).
+typedef __attribute__((address_space(3))) const u64 lds_cu64;
+typedef __attribute__((address_space(3))) const u32 lds_cu32;
+typedef __attribute__((address_space(3))) const u16 lds_cu16;
+typedef __attribute__((address_space(3))) const u8 lds_cu8;
+
+// Wide walk of one batch of k_scan5<true>: returns the pairs this thread
+// evaluated. Consecutive lanes take consecutive rows d of one word group,
+// last group first (it has the most rows, so the per-lane search for the
+// group is short). A wave holds one triple and mostly one group: its lanes
+// read the same G dwords (LDS broadcast), and each brings its own td. Not
+// inlined: the kernel's other walk needs most of the register file, and
+// inside the kernel this loop's invariants were spilled and reloaded from
+// scratch in every task; as a function it gets registers of its own.
+template <int STR>
+__device__ __attribute__((noinline)) u64 scan5_wide_walk(
+    const ScanArgs& args, DevCtl* ctl, int pad, int total_tasks,
+    lds_cu64* l_pool, lds_cu32* l_G, lds_cu32* l_tpre, lds_cu32* l_rec,
+    lds_cu8* l_pos, lds_cu64* l_H1, lds_cu64* l_H0, lds_cu16* l_abc,
+    lds_cu64* l_base) {
+  constexpr int NW = SCAN5_WIDE_WORDS;
+  constexpr int GB = SCAN5_WIDE_GB;
+  const u64* s_pool = (const u64*)l_pool;
+  const u32* s_G = (const u32*)l_G;
+  const u32* s_tpre = (const u32*)l_tpre;                      // [TB + 1]
+  const u32 (*s_rec)[16] = (const u32 (*)[16])l_rec;          // [TB]
+  const u8 (*s_pos)[GT_LIST_BYTES] = (const u8 (*)[GT_LIST_BYTES])l_pos;
+  const u64 (*s_H1)[8][4] = (const u64 (*)[8][4])l_H1;        // [TB]
+  const u64 (*s_H0)[8][4] = (const u64 (*)[8][4])l_H0;
+  const u16 (*s_abc)[3] = (const u16 (*)[3])l_abc;            // [TB]
+  const i64* s_base = (const i64*)l_base;                      // [TB]
+  const int n = args.n;
+  const int count_all = args.count_all;
+  const u64 excl = args.excl;
+  u64 local_eval = 0;
+  int since_poll = 0;
+  for (int task = threadIdx.x; task < total_tasks; task += blockDim.x) {
+    if (!count_all) {
+      since_poll += GB;
+      if (since_poll >= 64) {
+        since_poll = 0;
+        if (dev_abort(ctl)) break;
+      }
+    }
+    // Task counts are padded to the wave size, so a wave holds one
+    // triple: the one of its first task, found by 8 lanes at once.
+    const int task0 = __builtin_amdgcn_readfirstlane(task);
+    const u64 below = __ballot(
+        static_cast<int>(s_tpre[1 + (threadIdx.x & 7)]) <= task0);
+    const int t = __popc(static_cast<u32>(below) & ((1u << TB) - 1u));
+    // The triple's record, through scalars.
+    const lds_u32x4* rec = reinterpret_cast<const lds_u32x4*>(s_rec[t]);
+    const lds_u32x4 ra = rec[0], rh1 = rec[2], rh0 = rec[3];
+    const lds_u32x2 rb = *reinterpret_cast<const lds_u32x2*>(&s_rec[t][4]);
+    const int tpre = __builtin_amdgcn_readfirstlane(ra.x);
+    const int cnt = __builtin_amdgcn_readfirstlane(ra.y);
+    const int lo = __builtin_amdgcn_readfirstlane(ra.z);
+    const int hi = __builtin_amdgcn_readfirstlane(ra.w);
+    const u32 ids = dev_uniform(rb.x);
+    const u32 lens = dev_uniform(rb.y);
+    const u32 head1[4] = {dev_uniform(rh1.x), dev_uniform(rh1.y),
+                          dev_uniform(rh1.z), dev_uniform(rh1.w)};
+    const u32 head0[4] = {dev_uniform(rh0.x), dev_uniform(rh0.y),
+                          dev_uniform(rh0.z), dev_uniform(rh0.w)};
+    const int task_t = task - tpre;
+    if (task_t >= cnt) continue;
+    // Bit i of the task is the pair (d, e0 + i), flat index q0 + i;
+    // valid: clipped to e > d and to the triple's [lo, hi) window,
+    // without the excluded gates.
+    const Scan5WideTask wt =
+        scan5_wide_decode(n, pad, static_cast<int>(ids & 0xffffu), task_t);
+    const int wg = wt.wg, d = wt.d, e0 = wt.e0, q0 = wt.q0;
+    const u64 valid = scan5_wide_valid(wt, lo, hi, excl);
+    if (valid == 0) continue;
+    local_eval += __popcll(valid);
+
+    // Screen: the listed positions of the screen cell. Per position the
+    // lanes read G at their candidate words (the same address across most
+    // of a wave: LDS broadcast) and at d's own word for td's bit. A cell
+    // that is not live has one side empty and rejects nothing, as in the
+    // short walk.
+    const u32 live = (ids >> 16) & 0xffu;
+    const int u0 = static_cast<int>(ids >> 24);
+    const int n1 = static_cast<int>(lens & 0x3ffu);
+    const int n0 = static_cast<int>((lens >> 10) & 0x3ffu);
+    GtWords<NW> vw;
+#pragma unroll
+    for (int k = 0; k < NW; k++) {
+      vw.w[k] = static_cast<u32>(valid >> (32 * k));
+    }
+    const GtWords<NW> pw = gt_screen<NW>(
+        head1, head0, s_pos[t], n1, s_pos[t] + (lens >> 20), n0,
+        &s_G[NW * wg], &s_G[(d + pad) >> 5], (d + pad) & 31, vw);
+    u64 pend = 0;
+#pragma unroll
+    for (int k = 0; k < NW; k++) {
+      pend |= static_cast<u64>(pw.w[k]) << (32 * k);
+    }
+
+    // Rare path. The screen only ever passes too much.
+    while (pend != 0) {
+      const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
+      pend &= pend - 1;
+      scan5_after_screen<STR>(args, ctl, s_pool, s_H1[t], s_H0[t], s_abc[t],
+                              live & ~(1u << u0), s_base[t] + q0 + i, d,
+                              e0 + i);
+    }
+  }
+  return local_eval;
+}
+
 // WIDE: the variant for pools with rows longer than SCAN5_WIDE_MIN_ROW. It
 // keeps the gate-transposed pool in LDS next to the row-form pool (at the
 // dense stride, to stay within a quarter of a CU's LDS) and sends every
@@ -207,17 +320,21 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   // pool's last gate inside the array (their content is masked out).
   constexpr int STR = WIDE ? PSTR_DENSE : PSTR;
   constexpr int SEG = 4, LG_SEG = 2;
-  // Wide walk: a task screens the 32 NW gates of NW aligned words of G.
-  constexpr int NW = SCAN5_WIDE_WORDS;
-  constexpr int GB = 32 * NW;
+  // Wide walk: a task screens the 32 NW gates of NW aligned words of G
+  // (geometry: sbg/scan5_geom.hpp).
   __shared__ alignas(16) u64 s_pool[(MAX_GATES + SEG) * STR];
   __shared__ alignas(16) u32 s_G[WIDE ? GT_DWORDS : 1];
-  __shared__ int s_cnt[TB];      // wide walk: tasks per triple, unpadded
   __shared__ int s_wide;         // this batch takes the wide walk
   // Wide walk: position lists of each triple's screen cell (see
-  // gt_build_lists), their padded lengths and the target-0 list's offset.
+  // gt_build_lists).
   __shared__ alignas(16) u8 s_pos[WIDE ? TB : 1][GT_LIST_BYTES];
-  __shared__ int s_npos[TB][3];
+  // Wide walk: all that a task needs of its triple before the G reads, in
+  // one record that a wave fetches at one address in one round trip.
+  // Dwords: 0 the triple's first task, 1 its task count (unpadded), 2 and 3
+  // the window [lo, hi), 4 c | live << 16 | screen cell << 24, 5 the lists'
+  // padded lengths and the target-0 list's offset, 10 bits each, 8..11 and
+  // 12..15 the first 16 positions of the target-1 and the target-0 list.
+  __shared__ alignas(16) u32 s_rec[WIDE ? TB : 1][16];
   __shared__ alignas(16) u64 s_H1[TB][8][4];
   __shared__ alignas(16) u64 s_H0[TB][8][4];
   __shared__ i64 s_base[TB];     // flat-rank base of each triple
@@ -234,11 +351,12 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   __shared__ int s_stop;         // all triples past range end
 
   const int n = args.n;
+  const int pad = scan5_wide_pad(n);  // shift of the gate ids inside G
   load_pool_lds<STR>(s_pool, args.pool, n);
   if constexpr (WIDE) {
     __syncthreads();
     // Published by the barriers of the first dequeue.
-    build_gate_transposed_lds<STR>(s_G, s_pool, n);
+    build_gate_transposed_lds<STR>(s_G, s_pool, n, pad);
   }
 
   DevCtl* ctl = args.ctl;
@@ -280,12 +398,12 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       //
       // A batch whose longest row exceeds SCAN5_WIDE_MIN_ROW takes the wide
       // walk instead. A task there is (triple, row d, word group Wg): the
-      // pairs (d, e) with e among the GB gates [GB Wg, GB Wg + GB), aligned
-      // to absolute gate ids so that G indexes directly. Group Wg has the
-      // rows c < d <= min(n - 2, GB Wg + GB - 2); only the last group,
-      // (n - 1) / GB, is cut by n - 2 and has all m - 1 rows. Each
-      // triple's task count is padded to a multiple of 64 so that a wave
-      // never holds two triples and the walk's position loop is scalar.
+      // pairs (d, e) with e among the GB gates of G's words [NW Wg,
+      // NW Wg + NW), whose ids are shifted by pad so that the pool's last
+      // gate ends the last group; the ids that no gate has are the low
+      // bits of group 0, which has the fewest rows. Each triple's task
+      // count is padded to a multiple of 64 so that a wave never holds two
+      // triples and the walk's position loop is scalar.
       int mmax = 0;
       for (int t = 0; t < TB; t++) {
         if (s_prefix[t + 1] != 0 && s_m[t] > mmax) mmax = s_m[t];
@@ -298,18 +416,18 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
         if (s_prefix[t + 1] != 0) {
           const int rows = s_m[t] - 1;
           if (wide) {
-            const int c = n - 1 - s_m[t];
-            const int w_min = (c + 2) / GB, w_max = (n - 1) / GB;
-            const int k = w_max - w_min;  // groups not cut by n - 2
-            cnt = rows + k * (GB - 2 - c) + GB * (k * (w_min + w_max - 1) / 2);
-            s_cnt[t] = cnt;
+            cnt = scan5_wide_task_count(n, pad, n - 1 - s_m[t]);
+            if constexpr (WIDE) {
+              s_rec[t][0] = static_cast<u32>(s_tpre[t]);
+              s_rec[t][1] = static_cast<u32>(cnt);
+              s_rec[t][2] = static_cast<u32>(s_lo[t]);
+              s_rec[t][3] = static_cast<u32>(s_hi[t]);
+            }
             cnt = (cnt + 63) & ~63;
           } else {
             const int ns = (rows + SEG - 1) >> LG_SEG;
             cnt = ns * rows - SEG * (ns * (ns - 1) / 2);
           }
-        } else if (wide) {
-          s_cnt[t] = 0;
         }
         s_tpre[t + 1] = s_tpre[t] + cnt;
       }
@@ -344,8 +462,17 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       const int t = threadIdx.x >> 5;
       if (s_prefix[t + 1] != s_prefix[t]) {  // else: cells not built
         const int u0 = 7 - static_cast<int>(s_best[t] & 7u);
-        gt_build_lists(s_H1[t][u0], s_H0[t][u0], s_pos[t], s_npos[t],
+        int counts[3];
+        gt_build_lists(s_H1[t][u0], s_H0[t][u0], s_pos[t],
+                       reinterpret_cast<u8*>(&s_rec[t][8]), counts,
                        threadIdx.x & 31);
+        if ((threadIdx.x & 31) == 0) {
+          s_rec[t][4] = static_cast<u32>(n - 1 - s_m[t]) | (s_live[t] << 16) |
+                        (static_cast<u32>(u0) << 24);
+          s_rec[t][5] = static_cast<u32>(counts[0]) |
+                        (static_cast<u32>(counts[1]) << 10) |
+                        (static_cast<u32>(counts[2]) << 20);
+        }
       }
       __syncthreads();
     }
@@ -353,89 +480,16 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
     const int total_tasks = s_tpre[TB];
     int since_poll = 0;
 
-    // Wide walk. Consecutive lanes take consecutive rows d of one word
-    // group, last group first (it has the most rows, so the per-lane search
-    // for the group is short). A wave holds one triple and mostly one
-    // group: its lanes read the same G dwords (LDS broadcast), and each
-    // brings its own td.
-    if (WIDE && s_wide) {
-      for (int task = threadIdx.x; task < total_tasks; task += blockDim.x) {
-        if (!args.count_all) {
-          since_poll += GB;
-          if (since_poll >= 64) {
-            since_poll = 0;
-            if (dev_abort(ctl)) break;
-          }
-        }
-        int t = 0;
-        while (s_tpre[t + 1] <= task) t++;
-        // Task counts are padded to the wave size: one triple per wave.
-        t = __builtin_amdgcn_readfirstlane(t);
-        int d2 = task - s_tpre[t];
-        if (d2 >= s_cnt[t]) continue;
-        const int m = s_m[t];
-        const int c = n - 1 - m;
-        int wg = (n - 1) / GB;
-        for (int rows = m - 1; d2 >= rows; rows = GB * wg + GB - 2 - c) {
-          d2 -= rows;
-          wg--;
-        }
-        const int d = c + 1 + d2;
-        const int e0 = GB * wg;  // gate of bit 0
-        // Flat pair index of bit 0 (negative where e0 <= d): bit i is the
-        // pair (d, e0 + i). Clip bits to e > d, to the pool's end and to
-        // the triple's [lo, hi) window.
-        const int q0 = d2 * m - d2 * (d2 + 1) / 2 + e0 - d - 1;
-        int i_lo = d + 1 - e0;
-        if (i_lo < 0) i_lo = 0;
-        const int lo = static_cast<int>(s_lo[t]);
-        if (i_lo < lo - q0) i_lo = lo - q0;
-        int i_hi = n - e0;
-        if (i_hi > GB) i_hi = GB;
-        if (i_hi > s_hi[t] - q0) i_hi = s_hi[t] - q0;
-        if (i_lo >= i_hi) continue;
-        u64 valid = (~0ULL >> (64 - i_hi)) & (~0ULL << i_lo);  // 1 <= i_hi
-        if (args.excl != 0) {
-          // An excluded d drops the whole row; excluded e's (ids < 64 only)
-          // drop out of the mask with one shift per task.
-          if (dev_excluded(args.excl, d)) continue;
-          if (e0 < 64) valid &= ~(args.excl >> e0);
-        }
-        local_eval += __popcll(valid);
-
-        // Screen: the listed positions of the screen cell. Per position
-        // the lanes read G at their candidate words (the same address
-        // across most of a wave: LDS broadcast) and at d's own word for
-        // td's bit. A cell that is not live has one side empty and rejects
-        // nothing, as in the short walk.
-        const u32 live = s_live[t];
-        const int u0 = 7 - static_cast<int>(s_best[t] & 7u);
-        const int n1 = __builtin_amdgcn_readfirstlane(s_npos[t][0]);
-        const int n0 = __builtin_amdgcn_readfirstlane(s_npos[t][1]);
-        GtWords<NW> vw;
-#pragma unroll
-        for (int k = 0; k < NW; k++) {
-          vw.w[k] = static_cast<u32>(valid >> (32 * k));
-        }
-        const GtWords<NW> pw =
-            gt_screen<NW>(s_pos[t], n1, s_pos[t] + s_npos[t][2], n0,
-                          &s_G[NW * wg], &s_G[d >> 5], d & 31, vw);
-        u64 pend = 0;
-#pragma unroll
-        for (int k = 0; k < NW; k++) {
-          pend |= static_cast<u64>(pw.w[k]) << (32 * k);
-        }
-
-        // Rare path. The screen only ever passes too much.
-        while (pend != 0) {
-          const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
-          pend &= pend - 1;
-          scan5_after_screen<STR>(args, ctl, s_pool, s_H1[t], s_H0[t],
-                                  s_abc[t], live & ~(1u << u0),
-                                  s_base[t] + q0 + i, d, e0 + i);
-        }
+    // Wide walk (scan5_wide_walk).
+    if constexpr (WIDE) {
+      if (s_wide) {
+        local_eval += scan5_wide_walk<STR>(
+            args, ctl, pad, total_tasks, (lds_cu64*)s_pool, (lds_cu32*)s_G,
+            (lds_cu32*)s_tpre, (lds_cu32*)s_rec, (lds_cu8*)s_pos,
+            (lds_cu64*)s_H1, (lds_cu64*)s_H0, (lds_cu16*)s_abc,
+            (lds_cu64*)s_base);
+        continue;
       }
-      continue;
     }
 
     // Row-segment walk. Consecutive lanes take consecutive rows d2 of one

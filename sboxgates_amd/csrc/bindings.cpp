@@ -474,17 +474,11 @@ PYBIND11_MODULE(_core, m) {
       .def("scan_pool", [](Engine& e, int k, const state& st, py::bytes target,
                            py::bytes mask, i64 begin, i64 end, u64 seed,
                            bool count_all, u64 excl) {
-        std::vector<ttable> pool(st.num_gates);
-        for (int i = 0; i < st.num_gates; i++) pool[i] = st.gates[i].table;
-        ScanRequest rq;
-        rq.tables = pool.data();
-        rq.n = st.num_gates;
-        rq.target = tt_from_bytes(target);
-        rq.mask = tt_from_bytes(mask);
-        rq.excl_low64 = excl;
-        rq.seed = seed;
+        std::vector<ttable> pool;
+        ScanRequest rq = make_scan_request(pool, st, tt_from_bytes(target),
+                                           tt_from_bytes(mask), seed, excl,
+                                           k == 4 ? e.matcher3() : nullptr);
         rq.count_all = count_all;
-        if (k == 4) rq.matcher = e.matcher3();
         ScanResult r = e.scan(k, rq, begin, end);
         std::vector<int> res(r.res, r.res + 10);
         return py::make_tuple(r.found, res, r.evaluated);

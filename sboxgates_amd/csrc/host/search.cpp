@@ -205,9 +205,12 @@ static void fill_halves(GateHalves* out, const state* st, int n, const ttable& T
 
 // 4-cell requirements for a pair (x, y): bit p of req*/care is pattern
 // p = vx<<1 | vy. Returns false if some cell is contradictory (no 2-input
-// function can match).
-static bool pair_requirements(const GateHalves& x, const GateHalves& y, u8* req1,
-                              u8* care) {
+// function can match). Kept out of line: on its own the compiler vectorizes
+// the cells; inlined into the pair sweep it emits scalar code with spills
+// and step 3 measured 6 % slower.
+[[gnu::noinline]] static bool pair_requirements(const GateHalves& x,
+                                                const GateHalves& y, u8* req1,
+                                                u8* care) {
   u8 r1 = 0, r0 = 0;
   for (int p = 0; p < 4; p++) {
     bool has1 = tt_any((p & 2 ? x.p : x.q) & (p & 1 ? y.p : y.q));
@@ -234,6 +237,55 @@ static inline u8 fun2_pattern_table(u8 fun) {
 static inline u8 swap_pair_patterns(u8 m) {
   return static_cast<u8>((m & 0x9) | ((m & 2) << 1) | ((m & 4) >> 1));
 }
+
+// The calling thread's halves buffer. Step 3 fills it and step 4a of the same
+// node reads it, both before step 5 recurses, so one per thread is enough.
+static std::vector<GateHalves>& halves_scratch() {
+  static thread_local std::vector<GateHalves> halves;
+  return halves;
+}
+
+// The pair sweep of steps 3 and 4a: the first pair of gates, in visit order,
+// that a function of `funs` (ended by num_inputs == 0) combines into the
+// target, in either argument order. A match ends the sweep with what
+// appending the function returned, which is NO_GATE when the bounds forbid
+// the append; no match is an empty optional. Via 4-cell forced-bit
+// requirements instead of per-function truth-table evaluation; masked
+// equality (see header note).
+static inline std::optional<gatenum> pair_sweep(
+    state* st, const ttable& target, const ttable& mask, const GateHalves* halves,
+    const gatenum* order, const boolfunc* funs, metric_t metric, const char* where) {
+  for (int i = 0; i < st->num_gates; i++) {
+    const gatenum gi = order[i];
+    for (int k = i + 1; k < st->num_gates; k++) {
+      const gatenum gk = order[k];
+      u8 req1, care;
+      if (!pair_requirements(halves[gi], halves[gk], &req1, &care)) continue;
+      const u8 req1s = swap_pair_patterns(req1);
+      const u8 cares = swap_pair_patterns(care);
+      for (int m = 0; funs[m].num_inputs != 0; m++) {
+        const u8 fpat = fun2_pattern_table(funs[m].fun);
+        if ((fpat & care) == req1) {
+          return assert_ret(add_boolfunc_2(st, funs[m], gi, gk, metric), target, st,
+                            mask, where);
+        }
+        if (!funs[m].ab_commutative && (fpat & cares) == req1s) {
+          return assert_ret(add_boolfunc_2(st, funs[m], gk, gi, metric), target, st,
+                            mask, where);
+        }
+      }
+    }
+  }
+  return std::nullopt;
+}
+
+// Adds its lifetime to a phase counter of SearchStats.
+struct PhaseTimer {
+  using clock = std::chrono::steady_clock;
+  double* acc;
+  clock::time_point t0 = clock::now();
+  ~PhaseTimer() { *acc += std::chrono::duration<double>(clock::now() - t0).count(); }
+};
 
 // ---------------------------------------------------------------------------
 // Engine
@@ -406,20 +458,8 @@ bool Engine::dist_scan_chunked(int k, const ScanRequest& rq, u64 chunk, u16 res[
 bool Engine::distributed_lut_body(const WorkMsg& w, u16 res[10], bool* found5) {
   // Build the pool view. The tables live inside the (broadcast) state.
   static thread_local std::vector<ttable> pool;
-  pool.resize(w.st.num_gates);
-  for (int i = 0; i < w.st.num_gates; i++) pool[i] = w.st.gates[i].table;
-
-  ScanRequest rq;
-  rq.tables = pool.data();
-  rq.n = w.st.num_gates;
-  rq.target = w.target;
-  rq.mask = w.mask;
-  rq.seed = w.seed;
-  rq.count_all = false;
-  rq.excl_low64 = 0;
-  for (int i = 0; i < 8 && w.inbits[i] != -1; i++) {
-    if (w.inbits[i] < 64) rq.excl_low64 |= 1ULL << w.inbits[i];
-  }
+  const ScanRequest rq = make_scan_request(pool, w.st, w.target, w.mask, w.seed,
+                                           excl_from_inbits(w.inbits));
 
   *found5 = false;
   // 5/7-LUT chunk sizes: fixed constants (env-overridable for tests) so
@@ -469,20 +509,12 @@ void Engine::stop_workers() {
 }
 
 gatenum Engine::lut_search(state* st, const ttable& target, const ttable& mask,
-                           const i8* inbits, const gatenum* gate_order) {
+                           const i8* inbits) {
   // --- 3-LUT scan (local to rank 0; parity: lut.c:501-523). ---
   {
     static thread_local std::vector<ttable> pool;
-    pool.resize(st->num_gates);
-    for (int i = 0; i < st->num_gates; i++) pool[i] = st->gates[i].table;
-    ScanRequest rq;
-    rq.tables = pool.data();
-    rq.n = st->num_gates;
-    rq.target = target;
-    rq.mask = mask;
-    rq.seed = rng_.next();
-    rq.count_all = false;
-    rq.excl_low64 = 0;  // reference parity: 3-LUT scan ignores inbits
+    // No exclusions: reference parity, the 3-LUT scan ignores inbits.
+    const ScanRequest rq = make_scan_request(pool, *st, target, mask, rng_.next());
     ScanResult r = scan(3, rq, 0, n_choose_k(rq.n, 3));
     if (r.found) {
       const ttable& ta = st->gates[r.res[1]].table;
@@ -493,7 +525,6 @@ gatenum Engine::lut_search(state* st, const ttable& target, const ttable& mask,
           add_lut(st, static_cast<u8>(r.res[0]), nt, r.res[1], r.res[2], r.res[3]),
           target, st, mask, "lut_search/3");
     }
-    (void)gate_order;
   }
 
   if (!check_num_gates_possible(st, 2, 0, opt_.metric)) return NO_GATE;
@@ -558,167 +589,153 @@ gatenum Engine::lut_search(state* st, const ttable& target, const ttable& mask,
   return NO_GATE;
 }
 
+// ---------------------------------------------------------------------------
+// create_circuit: one recursion node of Kwan's algorithm.
+// ---------------------------------------------------------------------------
+
+// Step 1: an existing gate already realizes the map (sboxgates.c:301-308).
+static std::optional<gatenum> step1_existing(state* st, const ttable& target,
+                                             const ttable& mask,
+                                             const gatenum* order) {
+  for (int i = 0; i < st->num_gates; i++) {
+    if (tt_eq_mask(target, st->gates[order[i]].table, mask)) {
+      return assert_ret(order[i], target, st, mask, "step1");
+    }
+  }
+  return std::nullopt;
+}
+
+// Step 2: an inverse realizes the map -> append NOT (sboxgates.c:310-321).
+static std::optional<gatenum> step2_inverted(state* st, const ttable& target,
+                                             const ttable& mask,
+                                             const gatenum* order, metric_t metric) {
+  if (!check_num_gates_possible(st, 1, sat_metric_of(NOT), metric)) return NO_GATE;
+  for (int i = 0; i < st->num_gates; i++) {
+    if (tt_eq_mask(target, ~st->gates[order[i]].table, mask)) {
+      return assert_ret(add_not_gate(st, order[i], metric), target, st, mask, "step2");
+    }
+  }
+  return std::nullopt;
+}
+
 gatenum Engine::create_circuit(state* st, const ttable& target, const ttable& mask,
                                const i8* inbits) {
-  // Randomized gate visit order (parity: sboxgates.c:285-299).
-  gatenum gate_order[MAX_GATES];
-  for (int i = 0; i < st->num_gates; i++) {
-    gate_order[i] = static_cast<gatenum>(st->num_gates - 1 - i);
+  gatenum order[MAX_GATES];
+  order_gates(*st, order);
+  stats_.nodes += 1;
+
+  std::optional<gatenum> done;
+  {
+    PhaseTimer timer{&stats_.step12_seconds};
+    if ((done = step1_existing(st, target, mask, order))) return *done;
+    if ((done = step2_inverted(st, target, mask, order, opt_.metric))) return *done;
+  }
+  if ((done = step3_pairs(st, target, mask, order))) return *done;
+  if (opt_.lut_graph) {
+    gatenum ret = lut_search(st, target, mask, inbits);
+    if (ret != NO_GATE) return assert_ret(ret, target, st, mask, "lut_search");
+  } else {
+    if ((done = step4a_not_pairs(st, target, mask, order))) return *done;
+    if ((done = step4b_triples(st, target, mask))) return *done;
+  }
+  return step5_multiplex(st, target, mask, inbits);
+}
+
+// Randomized gate visit order (parity: sboxgates.c:285-299).
+void Engine::order_gates(const state& st, gatenum* order) {
+  for (int i = 0; i < st.num_gates; i++) {
+    order[i] = static_cast<gatenum>(st.num_gates - 1 - i);
   }
   if (opt_.randomize) {
-    for (u32 i = st->num_gates - 1; i > 0; i--) {
-      u64 j = rng_.below(i + 1);
-      gatenum t = gate_order[i];
-      gate_order[i] = gate_order[j];
-      gate_order[j] = t;
+    for (u32 i = st.num_gates - 1; i > 0; i--) {
+      std::swap(order[i], order[rng_.below(i + 1)]);
     }
   }
+}
 
-  const ttable T1 = target & mask;
-  const ttable T0 = ~target & mask;
-  stats_.nodes += 1;
-  const auto t_s12 = std::chrono::steady_clock::now();
-
-  // Step 1: an existing gate already realizes the map (sboxgates.c:301-308).
-  for (int i = 0; i < st->num_gates; i++) {
-    if (tt_eq_mask(target, st->gates[gate_order[i]].table, mask)) {
-      return assert_ret(gate_order[i], target, st, mask, "step1");
-    }
-  }
-
-  // Step 2: an inverse realizes the map -> append NOT (sboxgates.c:310-321).
-  if (!check_num_gates_possible(st, 1, sat_metric_of(NOT), opt_.metric)) {
-    return NO_GATE;
-  }
-  for (int i = 0; i < st->num_gates; i++) {
-    if (tt_eq_mask(target, ~st->gates[gate_order[i]].table, mask)) {
-      return assert_ret(add_not_gate(st, gate_order[i], opt_.metric), target, st,
-                        mask, "step2");
-    }
-  }
-  stats_.step12_seconds +=
-      std::chrono::duration<double>(std::chrono::steady_clock::now() - t_s12)
-          .count();
-
-  // Step 3: a pair combined by one available gate (sboxgates.c:323-350).
-  // Implemented via 4-cell forced-bit requirements instead of per-function
-  // truth-table evaluation; masked equality (see header note).
+// Step 3: a pair combined by one available gate (sboxgates.c:323-350).
+std::optional<gatenum> Engine::step3_pairs(state* st, const ttable& target,
+                                           const ttable& mask, const gatenum* order) {
   if (!check_num_gates_possible(st, 1, sat_metric_of(AND), opt_.metric)) {
     return NO_GATE;
   }
-  struct PhaseTimer {
-    double* acc;
-    std::chrono::steady_clock::time_point t0;
-    explicit PhaseTimer(double* a) : acc(a), t0(std::chrono::steady_clock::now()) {}
-    ~PhaseTimer() {
-      *acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0)
-                  .count();
-    }
-  };
-  static thread_local std::vector<GateHalves> halves;
+  std::vector<GateHalves>& halves = halves_scratch();
   halves.resize(st->num_gates);
-  fill_halves(halves.data(), st, st->num_gates, T1, T0);
-  {
-  PhaseTimer pt3(&stats_.step3_seconds);
-  for (int i = 0; i < st->num_gates; i++) {
-    const gatenum gi = gate_order[i];
-    for (int k = i + 1; k < st->num_gates; k++) {
-      const gatenum gk = gate_order[k];
-      u8 req1, care;
-      if (!pair_requirements(halves[gi], halves[gk], &req1, &care)) continue;
-      const u8 req1s = swap_pair_patterns(req1);
-      const u8 cares = swap_pair_patterns(care);
-      for (int m = 0; opt_.avail_gates[m].num_inputs != 0; m++) {
-        const u8 fpat = fun2_pattern_table(opt_.avail_gates[m].fun);
-        if ((fpat & care) == req1) {
-          return assert_ret(add_boolfunc_2(st, opt_.avail_gates[m], gi, gk, opt_.metric),
-                            target, st, mask, "step3");
-        }
-        if (!opt_.avail_gates[m].ab_commutative && (fpat & cares) == req1s) {
-          return assert_ret(add_boolfunc_2(st, opt_.avail_gates[m], gk, gi, opt_.metric),
-                            target, st, mask, "step3");
-        }
-      }
-    }
-  }
-  }
+  fill_halves(halves.data(), st, st->num_gates, target & mask, ~target & mask);
+  PhaseTimer timer{&stats_.step3_seconds};
+  return pair_sweep(st, target, mask, halves.data(), order, opt_.avail_gates,
+                    opt_.metric, "step3");
+}
 
-  if (opt_.lut_graph) {
-    gatenum ret = lut_search(st, target, mask, inbits, gate_order);
-    if (ret != NO_GATE) return assert_ret(ret, target, st, mask, "lut_search");
-  } else {
-    // Step 4a: pairs with NOT-augmented functions (sboxgates.c:358-386).
-    if (!check_num_gates_possible(st, 2, sat_metric_of(AND) + sat_metric_of(NOT),
-                                  opt_.metric)) {
-      return NO_GATE;
-    }
-    // Without -n the NOT-augmented function list is empty: the whole pair
-    // sweep would compute requirements for zero candidate functions (the
-    // reference pays this too, sboxgates.c:366-386 — measured at 22 s of
-    // the AES bit-0 CPU run).
-    if (opt_.avail_not[0].num_inputs != 0) {
-    PhaseTimer pt4a(&stats_.step4a_seconds);
-    for (int i = 0; i < st->num_gates; i++) {
-      const gatenum gi = gate_order[i];
-      for (int k = i + 1; k < st->num_gates; k++) {
-        const gatenum gk = gate_order[k];
-        u8 req1, care;
-        if (!pair_requirements(halves[gi], halves[gk], &req1, &care)) continue;
-        const u8 req1s = swap_pair_patterns(req1);
-        const u8 cares = swap_pair_patterns(care);
-        for (int m = 0; opt_.avail_not[m].num_inputs != 0; m++) {
-          const u8 fpat = fun2_pattern_table(opt_.avail_not[m].fun);
-          if ((fpat & care) == req1) {
-            return assert_ret(
-                add_boolfunc_2(st, opt_.avail_not[m], gi, gk, opt_.metric), target,
-                st, mask, "step4a");
-          }
-          if (!opt_.avail_not[m].ab_commutative && (fpat & cares) == req1s) {
-            return assert_ret(
-                add_boolfunc_2(st, opt_.avail_not[m], gk, gi, opt_.metric), target,
-                st, mask, "step4a");
-          }
-        }
-      }
-    }
-    }
-
-    // Step 4b: triples realized by an available composed 3-input function
-    // (sboxgates.c:388-435) — the gate-mode hot loop, run as a k=4 scan
-    // (GPU kernel k_scan4 on large pools): cell-requirement screen + one
-    // matcher-bitmap probe per argument order; all 6 orders (improvement
-    // over the reference's 4 orders with mis-indexed commutativity gates).
-    if (!check_num_gates_possible(st, 3, 2 * sat_metric_of(AND) + sat_metric_of(NOT),
-                                  opt_.metric)) {
-      return NO_GATE;
-    }
-    if (opt_.num_avail_3 > 0 && st->num_gates >= 3) {
-      static thread_local std::vector<ttable> pool4;
-      pool4.resize(st->num_gates);
-      for (int i = 0; i < st->num_gates; i++) pool4[i] = st->gates[i].table;
-      ScanRequest rq;
-      rq.tables = pool4.data();
-      rq.n = st->num_gates;
-      rq.target = target;
-      rq.mask = mask;
-      rq.excl_low64 = 0;
-      rq.seed = rng_.next();
-      rq.count_all = false;
-      rq.matcher = matcher3();
-      ScanResult r = scan(4, rq, 0, n_choose_k(rq.n, 3));
-      if (r.found) {
-        const boolfunc& f = opt_.avail_3[r.res[0]];
-        const int* sel = TRIPLE_PERMS6[r.res[1]];
-        const gatenum ids[3] = {r.res[2], r.res[3], r.res[4]};
-        return assert_ret(add_boolfunc_3(st, f, ids[sel[0]], ids[sel[1]],
-                                         ids[sel[2]], opt_.metric),
-                          target, st, mask, "step4b");
-      }
-    }
+// Step 4a: pairs with NOT-augmented functions (sboxgates.c:358-386), over
+// the halves that step 3 left.
+std::optional<gatenum> Engine::step4a_not_pairs(state* st, const ttable& target,
+                                                const ttable& mask,
+                                                const gatenum* order) {
+  if (!check_num_gates_possible(st, 2, sat_metric_of(AND) + sat_metric_of(NOT),
+                                opt_.metric)) {
+    return NO_GATE;
   }
+  // Without -n the NOT-augmented function list is empty: the whole pair
+  // sweep would compute requirements for zero candidate functions (the
+  // reference pays this too, sboxgates.c:366-386 — measured at 22 s of
+  // the AES bit-0 CPU run).
+  if (opt_.avail_not[0].num_inputs == 0) return std::nullopt;
+  PhaseTimer timer{&stats_.step4a_seconds};
+  return pair_sweep(st, target, mask, halves_scratch().data(), order,
+                    opt_.avail_not, opt_.metric, "step4a");
+}
 
-  // Step 5: multiplex on an input bit and recurse on the half-spaces
-  // (sboxgates.c:438-607).
+// Step 4b: triples realized by an available composed 3-input function
+// (sboxgates.c:388-435) — the gate-mode hot loop, run as a k=4 scan
+// (GPU kernel k_scan4 on large pools): cell-requirement screen + one
+// matcher-bitmap probe per argument order; all 6 orders (improvement
+// over the reference's 4 orders with mis-indexed commutativity gates).
+std::optional<gatenum> Engine::step4b_triples(state* st, const ttable& target,
+                                              const ttable& mask) {
+  if (!check_num_gates_possible(st, 3, 2 * sat_metric_of(AND) + sat_metric_of(NOT),
+                                opt_.metric)) {
+    return NO_GATE;
+  }
+  if (opt_.num_avail_3 <= 0 || st->num_gates < 3) return std::nullopt;
+  static thread_local std::vector<ttable> pool;
+  const ScanRequest rq =
+      make_scan_request(pool, *st, target, mask, rng_.next(), 0, matcher3());
+  ScanResult r = scan(4, rq, 0, n_choose_k(rq.n, 3));
+  if (!r.found) return std::nullopt;
+  const boolfunc& f = opt_.avail_3[r.res[0]];
+  const int* sel = TRIPLE_PERMS6[r.res[1]];
+  const gatenum ids[3] = {r.res[2], r.res[3], r.res[4]};
+  return assert_ret(
+      add_boolfunc_3(st, f, ids[sel[0]], ids[sel[1]], ids[sel[2]], opt_.metric),
+      target, st, mask, "step4b");
+}
+
+// Cross-bit branch-and-bound of step 5 (gate mode): once an earlier bit
+// produced `best`, later bits' candidates are only ever KEPT when strictly
+// smaller (ties keep the first), so bound their sub-searches to strictly
+// fewer gates. Measured: 3.4x fewer recursion nodes / 3.4x wall on AES
+// bit 0 (186 s -> 55 s CPU-only), at a ~0.4-gate mean cost on single-shot
+// runs (the tight bound reorders the greedy exploration) that -i 2 at the
+// higher speed more than recovers. Not applied in LUT mode (its searches
+// are scan-dominated; quality of the headline LUT artifacts stays
+// byte-for-byte reproducible) nor under the SAT metric (its bound check is
+// pre-append, so a tight bound would not be strict).
+// SBOXGATES_NO_PRUNE=1 disables.
+static gatenum cross_bit_bound(const options& opt, const state& best) {
+  static const bool prune_off = [] {
+    const char* e = std::getenv("SBOXGATES_NO_PRUNE");
+    return e != nullptr && e[0] != '\0' && e[0] != '0';
+  }();
+  const bool prune = !prune_off && opt.metric == METRIC_GATES && !opt.lut_graph &&
+                     best.num_gates >= 2;
+  return prune ? static_cast<gatenum>(best.num_gates - 2) : MAX_GATES;
+}
+
+// Step 5: multiplex on an input bit and recurse on the half-spaces
+// (sboxgates.c:438-607).
+gatenum Engine::step5_multiplex(state* st, const ttable& target, const ttable& mask,
+                                const i8* inbits) {
   i8 next_inbits[8];
   u8 bitp = 0;
   while (bitp < 6 && inbits[bitp] != -1) {
@@ -728,141 +745,29 @@ gatenum Engine::create_circuit(state* st, const ttable& target, const ttable& ma
   next_inbits[bitp] = -1;
   next_inbits[bitp + 1] = -1;
 
+  // best.num_gates == 0 (gates metric) or best.sat_metric == 0 (SAT metric)
+  // is "nothing kept yet".
   state best;
   gatenum best_out = NO_GATE;
   best.num_gates = 0;
   best.sat_metric = 0;
 
   for (int bit = 0; bit < get_num_inputs(st); bit++) {
-    bool skip = false;
-    for (int i = 0; i < bitp; i++) {
-      if (inbits[i] == bit) { skip = true; break; }
-    }
-    if (skip) continue;
+    if (std::find(inbits, inbits + bitp, bit) != inbits + bitp) continue;
     next_inbits[bitp] = static_cast<i8>(bit);
 
-    const ttable fsel = st->gates[bit].table;  // selection bit
     state nst;
-    gatenum nst_out = NO_GATE;
-
-    // Cross-bit branch-and-bound (gate mode): once an earlier bit
-    // produced `best`, later bits' candidates are only ever KEPT when
-    // strictly smaller (ties keep the first), so bound their sub-searches
-    // to strictly fewer gates. Measured: 3.4x fewer recursion nodes /
-    // 3.4x wall on AES bit 0 (186 s -> 55 s CPU-only), at a ~0.4-gate
-    // mean cost on single-shot runs (the tight bound reorders the greedy
-    // exploration) that -i 2 at the higher speed more than recovers.
-    // Not applied in LUT mode (its searches are scan-dominated; quality
-    // of the headline LUT artifacts stays byte-for-byte reproducible)
-    // nor under the SAT metric (its bound check is pre-append, so a
-    // tight bound would not be strict). SBOXGATES_NO_PRUNE=1 disables.
-    static const bool prune_off = [] {
-      const char* e = std::getenv("SBOXGATES_NO_PRUNE");
-      return e != nullptr && e[0] != '\0' && e[0] != '0';
-    }();
-    const bool have_best = best.num_gates != 0;
-    const gatenum best_bound =
-        !prune_off && have_best && opt_.metric == METRIC_GATES &&
-                !opt_.lut_graph && best.num_gates >= 2
-            ? static_cast<gatenum>(best.num_gates - 2)
-            : MAX_GATES;
-
-    if (opt_.lut_graph) {  // LUT-based multiplexer.
-      copy_state(nst, *st);
-      if (nst.max_gates > best_bound) nst.max_gates = best_bound;
-      nst.max_gates -= 1;  // Room for the multiplexer.
-      gatenum fb = create_circuit(&nst, target, mask & ~fsel, next_inbits);
-      if (fb == NO_GATE) continue;
-      gatenum fc = create_circuit(&nst, target, mask & fsel, next_inbits);
-      if (fc == NO_GATE) continue;
-      nst.max_gates = st->max_gates;  // restore the caller's bound exactly
-                                      // (it was clamped by best_bound)
-
-      if (fb == fc) {
-        nst_out = fb;
-      } else if (fb == bit) {
-        nst_out = add_and_gate(&nst, fb, fc, opt_.metric);
-        if (nst_out == NO_GATE) continue;
-      } else if (fc == bit) {
-        nst_out = add_or_gate(&nst, fb, fc, opt_.metric);
-        if (nst_out == NO_GATE) continue;
-      } else {
-        ttable mux_table = gen_lut_ttable(0xac, nst.gates[bit].table,
-                                          nst.gates[fb].table, nst.gates[fc].table);
-        nst_out = add_lut(&nst, 0xac, mux_table, static_cast<gatenum>(bit), fb, fc);
-        if (nst_out == NO_GATE) continue;
-      }
-      assert(tt_eq_mask(target, nst.gates[nst_out].table, mask));
-    } else {  // Try both AND- and OR-based multiplexers; keep the smaller.
-      state nst_and;
-      copy_state(nst_and, *st);
-      if (nst_and.max_gates > best_bound) nst_and.max_gates = best_bound;
-      nst_and.max_gates -= 2;
-      nst_and.max_sat_metric -= sat_metric_of(AND) + sat_metric_of(XOR);
-
-      gatenum mux_out_and = NO_GATE;
-      gatenum fb = create_circuit(&nst_and, target & ~fsel, mask & ~fsel, next_inbits);
-      if (fb != NO_GATE) {
-        gatenum fc = create_circuit(&nst_and, nst_and.gates[fb].table ^ target,
-                                    mask & fsel, next_inbits);
-        nst_and.max_gates = st->max_gates;  // caller's bound (was clamped)
-        nst_and.max_sat_metric += sat_metric_of(AND) + sat_metric_of(XOR);
-        gatenum andg = add_and_gate(&nst_and, fc, static_cast<gatenum>(bit), opt_.metric);
-        mux_out_and = add_xor_gate(&nst_and, fb, andg, opt_.metric);
-      }
-
-      state nst_or;
-      copy_state(nst_or, *st);
-      if (nst_or.max_gates > best_bound) nst_or.max_gates = best_bound;
-      if (mux_out_and != NO_GATE) {
-        nst_or.max_gates = nst_and.num_gates;
-        nst_or.max_sat_metric = nst_and.sat_metric;
-      }
-      nst_or.max_gates -= 2;
-      nst_or.max_sat_metric -= sat_metric_of(OR) + sat_metric_of(XOR);
-
-      gatenum mux_out_or = NO_GATE;
-      gatenum fd = create_circuit(&nst_or, ~target & fsel, mask & fsel, next_inbits);
-      if (fd != NO_GATE) {
-        gatenum fe = create_circuit(&nst_or, nst_or.gates[fd].table ^ target,
-                                    mask & ~fsel, next_inbits);
-        nst_or.max_gates += 2;
-        nst_or.max_sat_metric += sat_metric_of(OR) + sat_metric_of(XOR);
-        gatenum org = add_or_gate(&nst_or, fe, static_cast<gatenum>(bit), opt_.metric);
-        mux_out_or = add_xor_gate(&nst_or, fd, org, opt_.metric);
-        nst_or.max_gates = st->max_gates;
-        nst_or.max_sat_metric = st->max_sat_metric;
-      }
-      if (mux_out_and == NO_GATE && mux_out_or == NO_GATE) continue;
-
-      bool pick_and;
-      if (opt_.metric == METRIC_GATES) {
-        pick_and = mux_out_or == NO_GATE ||
-                   (mux_out_and != NO_GATE && nst_and.num_gates < nst_or.num_gates);
-      } else {
-        pick_and = mux_out_or == NO_GATE ||
-                   (mux_out_and != NO_GATE && nst_and.sat_metric < nst_or.sat_metric);
-      }
-      if (pick_and) {
-        copy_state(nst, nst_and);
-        nst_out = mux_out_and;
-      } else {
-        copy_state(nst, nst_or);
-        nst_out = mux_out_or;
-      }
-    }
+    const gatenum bound = cross_bit_bound(opt_, best);
+    const gatenum nst_out =
+        opt_.lut_graph ? mux_lut(*st, target, mask, bit, bound, next_inbits, &nst)
+                       : mux_and_or(*st, target, mask, bit, bound, next_inbits, &nst);
+    if (nst_out == NO_GATE) continue;
 
     // Keep the best sub-state by the active metric (sboxgates.c:593-606).
-    if (opt_.metric == METRIC_GATES) {
-      if (best.num_gates == 0 || nst.num_gates < best.num_gates) {
-        copy_state(best, nst);
-        best_out = nst_out;
-      }
-    } else {
-      if (best.sat_metric == 0 || nst.sat_metric < best.sat_metric) {
-        copy_state(best, nst);
-        best_out = nst_out;
-      }
+    if (metric_value(best, opt_.metric) == 0 ||
+        metric_value(nst, opt_.metric) < metric_value(best, opt_.metric)) {
+      copy_state(best, nst);
+      best_out = nst_out;
     }
   }
 
@@ -871,116 +776,209 @@ gatenum Engine::create_circuit(state* st, const ttable& target, const ttable& ma
   return assert_ret(best_out, target, st, mask, "step5");
 }
 
+// LUT-based multiplexer: both halves built in one state, joined by a 0xac
+// LUT unless a half is the selection bit itself.
+gatenum Engine::mux_lut(const state& st, const ttable& target, const ttable& mask,
+                        int bit, gatenum bound, const i8* next_inbits, state* nst) {
+  const ttable fsel = st.gates[bit].table;  // selection bit
+  copy_state(*nst, st);
+  if (nst->max_gates > bound) nst->max_gates = bound;
+  nst->max_gates -= 1;  // Room for the multiplexer.
+  gatenum fb = create_circuit(nst, target, mask & ~fsel, next_inbits);
+  if (fb == NO_GATE) return NO_GATE;
+  gatenum fc = create_circuit(nst, target, mask & fsel, next_inbits);
+  if (fc == NO_GATE) return NO_GATE;
+  nst->max_gates = st.max_gates;  // restore the caller's bound exactly
+                                  // (it was clamped by bound)
+
+  gatenum out;
+  if (fb == fc) {
+    out = fb;
+  } else if (fb == bit) {
+    out = add_and_gate(nst, fb, fc, opt_.metric);
+  } else if (fc == bit) {
+    out = add_or_gate(nst, fb, fc, opt_.metric);
+  } else {
+    ttable mux_table = gen_lut_ttable(0xac, nst->gates[bit].table,
+                                      nst->gates[fb].table, nst->gates[fc].table);
+    out = add_lut(nst, 0xac, mux_table, static_cast<gatenum>(bit), fb, fc);
+  }
+  assert(out == NO_GATE || tt_eq_mask(target, nst->gates[out].table, mask));
+  return out;
+}
+
+// Tries both the AND- and the OR-based multiplexer and keeps the smaller.
+// The two do not treat their bounds alike, and searches depend on it.
+gatenum Engine::mux_and_or(const state& st, const ttable& target, const ttable& mask,
+                           int bit, gatenum bound, const i8* next_inbits,
+                           state* nst) {
+  const ttable fsel = st.gates[bit].table;  // selection bit
+  state nst_and;
+  copy_state(nst_and, st);
+  if (nst_and.max_gates > bound) nst_and.max_gates = bound;
+  nst_and.max_gates -= 2;
+  nst_and.max_sat_metric -= sat_metric_of(AND) + sat_metric_of(XOR);
+
+  gatenum mux_out_and = NO_GATE;
+  gatenum fb = create_circuit(&nst_and, target & ~fsel, mask & ~fsel, next_inbits);
+  if (fb != NO_GATE) {
+    gatenum fc = create_circuit(&nst_and, nst_and.gates[fb].table ^ target,
+                                mask & fsel, next_inbits);
+    // The AND side goes back to the caller's gate bound outright (it was
+    // clamped by bound) before its two appends; its SAT bound by addition.
+    nst_and.max_gates = st.max_gates;
+    nst_and.max_sat_metric += sat_metric_of(AND) + sat_metric_of(XOR);
+    gatenum andg = add_and_gate(&nst_and, fc, static_cast<gatenum>(bit), opt_.metric);
+    mux_out_and = add_xor_gate(&nst_and, fb, andg, opt_.metric);
+  }
+
+  state nst_or;
+  copy_state(nst_or, st);
+  if (nst_or.max_gates > bound) nst_or.max_gates = bound;
+  // The OR side only has to beat the AND side, when that gave a result:
+  // both of its bounds then come from nst_and, not from the caller.
+  if (mux_out_and != NO_GATE) {
+    nst_or.max_gates = nst_and.num_gates;
+    nst_or.max_sat_metric = nst_and.sat_metric;
+  }
+  nst_or.max_gates -= 2;
+  nst_or.max_sat_metric -= sat_metric_of(OR) + sat_metric_of(XOR);
+
+  gatenum mux_out_or = NO_GATE;
+  gatenum fd = create_circuit(&nst_or, ~target & fsel, mask & fsel, next_inbits);
+  if (fd != NO_GATE) {
+    gatenum fe = create_circuit(&nst_or, nst_or.gates[fd].table ^ target,
+                                mask & ~fsel, next_inbits);
+    // Unlike the AND side, the OR side appends under its own bounds,
+    // restored by += 2, and takes the caller's only after the appends.
+    nst_or.max_gates += 2;
+    nst_or.max_sat_metric += sat_metric_of(OR) + sat_metric_of(XOR);
+    gatenum org = add_or_gate(&nst_or, fe, static_cast<gatenum>(bit), opt_.metric);
+    mux_out_or = add_xor_gate(&nst_or, fd, org, opt_.metric);
+    nst_or.max_gates = st.max_gates;
+    nst_or.max_sat_metric = st.max_sat_metric;
+  }
+  if (mux_out_and == NO_GATE && mux_out_or == NO_GATE) return NO_GATE;
+
+  const bool pick_and =
+      mux_out_or == NO_GATE ||
+      (mux_out_and != NO_GATE &&
+       metric_value(nst_and, opt_.metric) < metric_value(nst_or, opt_.metric));
+  copy_state(*nst, pick_and ? nst_and : nst_or);
+  return pick_and ? mux_out_and : mux_out_or;
+}
+
+// ---------------------------------------------------------------------------
+// Drivers
+// ---------------------------------------------------------------------------
+
 void Engine::save_checkpoint(const state& st) {
   if (!opt_.save_states) return;
   std::string path = save_state(st, opt_.output_dir);
   if (!path.empty()) saved_files_.push_back(path);
 }
 
-void Engine::generate_graph_one_output(const state& st_in) {
-  if (opt_.jobs > 1 && ctx_->world() == 1) {
-    generate_graph_one_output_jobs(st_in);
-    return;
-  }
-  // Parity: sboxgates.c:661-688.
-  assert(opt_.iterations > 0);
-  state st = st_in;
-  if (opt_.verbosity >= 0) {
-    std::printf("Generating graphs for output %d...\n", opt_.oneoutput);
-  }
-  for (int iter = 0; iter < opt_.iterations; iter++) {
-    state nst = st;
-    i8 bits[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    const ttable mask = tt_mask_for_inputs(get_num_inputs(&st));
-    nst.outputs[opt_.oneoutput] =
-        create_circuit(&nst, g_target_[opt_.oneoutput], mask, bits);
-    if (nst.outputs[opt_.oneoutput] == NO_GATE) {
-      if (opt_.verbosity >= 0) {
-        std::printf("(%d/%d): Not found.\n", iter + 1, opt_.iterations);
-      }
-      continue;
-    }
-    if (opt_.verbosity >= 0) {
-      std::printf("(%d/%d): %d gates. SAT metric: %d\n", iter + 1, opt_.iterations,
-                  nst.num_gates - get_num_inputs(&nst), nst.sat_metric);
-    }
-    save_checkpoint(nst);
-    if (opt_.metric == METRIC_GATES) {
-      if (nst.num_gates < st.max_gates) st.max_gates = nst.num_gates;
-    } else {
-      if (nst.sat_metric < st.max_sat_metric) st.max_sat_metric = nst.sat_metric;
-    }
-  }
+std::optional<state> Engine::search_output(const state& start, int output) {
+  std::optional<state> st(start);
+  i8 bits[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  const ttable mask = tt_mask_for_inputs(get_num_inputs(&start));
+  const gatenum out = create_circuit(&*st, g_target_[output], mask, bits);
+  if (out == NO_GATE) return std::nullopt;
+  assert(tt_eq_mask(g_target_[output], st->gates[out].table, mask));
+  st->outputs[output] = out;
+  return st;
 }
 
-// Parallel independent iterations: batches of `jobs` threads, each with
-// its own engine (rotating over visible GPUs when present); search bounds
-// tighten between batches. Semantics: the same iteration count as the
-// serial driver, with bound tightening at batch granularity instead of
-// per-iteration — every produced circuit is identical in kind and
-// checkpointed the same way.
-void Engine::generate_graph_one_output_jobs(const state& st_in) {
-  assert(opt_.iterations > 0);
-  state st = st_in;
-  if (opt_.verbosity >= 0) {
-    std::printf("Generating graphs for output %d (%d parallel jobs)...\n",
-                opt_.oneoutput, opt_.jobs);
-  }
+// A worker engine has this engine's options with jobs = 1, no output, the
+// job's seed, and the GPU at the job's place in its batch modulo the devices.
+void Engine::run_jobs(const std::vector<Job>& jobs,
+                      const std::function<void(Engine&, int)>& job,
+                      const std::function<void(int, int)>& after_batch) {
+  const int n = static_cast<int>(jobs.size());
   const int devices = gpu_ != nullptr ? std::max(1, gpu_count()) : 0;
-  int done = 0;
-  while (done < opt_.iterations) {
-    const int batch = std::min(opt_.jobs, opt_.iterations - done);
-    std::vector<state> results(batch);
-    std::vector<char> found(batch, 0);
+  for (int first = 0; first < n; first += opt_.jobs) {
+    const int count = std::min(opt_.jobs, n - first);
     std::vector<std::thread> threads;
-    for (int j = 0; j < batch; j++) {
-      threads.emplace_back([&, j] {
+    for (int j = 0; j < count; j++) {
+      threads.emplace_back([&, first, j] {
+        const int t = first + j;
         options wopt = opt_;
         wopt.jobs = 1;
         wopt.verbosity = -1;
-        if (wopt.seeded) wopt.seed = opt_.seed + 0x9E37 * (done + j + 1);
+        if (wopt.seeded) wopt.seed = jobs[t].seed;
         if (devices > 0) wopt.gpu_device = j % devices;
         try {
           Engine we(wopt);
           we.set_sbox(sbox_, num_inputs_);
-          state nst = st;
-          i8 bits[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-          const ttable mask = tt_mask_for_inputs(get_num_inputs(&st));
-          gatenum out = we.create_circuit(&nst, g_target_[opt_.oneoutput], mask,
-                                          bits);
-          if (out != NO_GATE) {
-            nst.outputs[opt_.oneoutput] = out;
-            results[j] = nst;
-            found[j] = 1;
-          }
+          job(we, t);
         } catch (const std::exception& e) {
-          std::fprintf(stderr, "search job %d failed: %s\n", done + j, e.what());
+          std::fprintf(stderr, "%s failed: %s\n", jobs[t].name.c_str(), e.what());
         }
       });
     }
     for (auto& t : threads) t.join();
-    for (int j = 0; j < batch; j++) {
-      if (!found[j]) {
-        if (opt_.verbosity >= 0) {
-          std::printf("(%d/%d): Not found.\n", done + j + 1, opt_.iterations);
-        }
-        continue;
-      }
-      const state& nst = results[j];
-      if (opt_.verbosity >= 0) {
-        std::printf("(%d/%d): %d gates. SAT metric: %d\n", done + j + 1,
-                    opt_.iterations, nst.num_gates - get_num_inputs(&nst),
-                    nst.sat_metric);
-      }
-      save_checkpoint(nst);
-      if (opt_.metric == METRIC_GATES) {
-        if (nst.num_gates < st.max_gates) st.max_gates = nst.num_gates;
-      } else {
-        if (nst.sat_metric < st.max_sat_metric) st.max_sat_metric = nst.sat_metric;
-      }
-    }
-    done += batch;
+    if (after_batch) after_batch(first, count);
   }
+}
+
+// The end of iteration `index` (from 1) of a single-output search: report
+// it, checkpoint what it found and tighten st's bound from that.
+void Engine::finish_iteration(int index, const std::optional<state>& found,
+                              state* st) {
+  if (!found) {
+    if (opt_.verbosity >= 0) {
+      std::printf("(%d/%d): Not found.\n", index, opt_.iterations);
+    }
+    return;
+  }
+  if (opt_.verbosity >= 0) {
+    std::printf("(%d/%d): %d gates. SAT metric: %d\n", index, opt_.iterations,
+                found->num_gates - get_num_inputs(&*found), found->sat_metric);
+  }
+  save_checkpoint(*found);
+  tighten_bound(*st, *found, opt_.metric);
+}
+
+void Engine::generate_graph_one_output(const state& st_in) {
+  assert(opt_.iterations > 0);
+  state st = st_in;
+  if (opt_.jobs <= 1 || ctx_->world() != 1) {
+    // Parity: sboxgates.c:661-688.
+    if (opt_.verbosity >= 0) {
+      std::printf("Generating graphs for output %d...\n", opt_.oneoutput);
+    }
+    for (int iter = 0; iter < opt_.iterations; iter++) {
+      finish_iteration(iter + 1, search_output(st, opt_.oneoutput), &st);
+    }
+    return;
+  }
+  // Parallel independent iterations: batches of `jobs` threads, each with
+  // its own engine (rotating over visible GPUs when present); search bounds
+  // tighten between batches. Semantics: the same iteration count as the
+  // serial driver, with bound tightening at batch granularity instead of
+  // per-iteration — every produced circuit is identical in kind and
+  // checkpointed the same way.
+  if (opt_.verbosity >= 0) {
+    std::printf("Generating graphs for output %d (%d parallel jobs)...\n",
+                opt_.oneoutput, opt_.jobs);
+  }
+  std::vector<Job> jobs;
+  for (int t = 0; t < opt_.iterations; t++) {
+    jobs.push_back({opt_.seed + 0x9E37 * (t + 1), "search job " + std::to_string(t)});
+  }
+  // One slot per thread of a batch: iteration t uses slot t % opt_.jobs.
+  std::vector<std::optional<state>> results(opt_.jobs);
+  run_jobs(
+      jobs,
+      [&](Engine& we, int t) {
+        results[t % opt_.jobs] = we.search_output(st, opt_.oneoutput);
+      },
+      [&](int first, int count) {
+        for (int t = first; t < first + count; t++) {
+          finish_iteration(t + 1, results[t % opt_.jobs], &st);
+          results[t % opt_.jobs].reset();
+        }
+      });
 }
 
 static int count_state_outputs(const state& st) {
@@ -1004,40 +1002,41 @@ void Engine::generate_graph(const state& st_in) {
   start_states[0] = st_in;
 
   const bool parallel = opt_.jobs > 1 && ctx_->world() == 1;
-  const int devices = gpu_ != nullptr ? std::max(1, gpu_count()) : 0;
 
   int num_outputs;
   while ((num_outputs = count_state_outputs(start_states[0])) < num_outputs_) {
-    gatenum max_gates = MAX_GATES;
-    int max_sat_metric = INT_MAX;
+    // Size of the states kept so far, and the bound of the searches to come.
+    int best = opt_.metric == METRIC_GATES ? MAX_GATES : INT_MAX;
     state out_states[20];
     int num_out_states = 0;
 
-    auto consider = [&](const state& st) {
-      // Fold a successful search result into the beam.
-      if (opt_.metric == METRIC_GATES) {
-        if (max_gates > st.num_gates) {
-          max_gates = st.num_gates;
-          num_out_states = 0;
+    struct Task {
+      int current;
+      u8 output;
+    };
+    auto start_of = [&](const Task& task) {
+      state st = start_states[task.current];
+      set_metric_bound(st, opt_.metric, best);
+      return st;
+    };
+    // Fold a search result into the beam.
+    auto fold = [&](const Task& task, const std::optional<state>& st) {
+      if (!st) {
+        if (opt_.verbosity >= 0) {
+          std::printf("No solution for output %d.\n", task.output);
         }
-        if (st.num_gates <= max_gates) {
-          if (num_out_states < std::min(20, opt_.beam)) {
-            out_states[num_out_states++] = st;
-          } else if (opt_.verbosity >= 0) {
-            std::printf("Output state buffer full! Throwing away valid state.\n");
-          }
-        }
-      } else {
-        if (max_sat_metric > st.sat_metric) {
-          max_sat_metric = st.sat_metric;
-          num_out_states = 0;
-        }
-        if (st.sat_metric <= max_sat_metric) {
-          if (num_out_states < std::min(20, opt_.beam)) {
-            out_states[num_out_states++] = st;
-          } else if (opt_.verbosity >= 0) {
-            std::printf("Output state buffer full! Throwing away valid state.\n");
-          }
+        return;
+      }
+      save_checkpoint(*st);
+      if (best > metric_value(*st, opt_.metric)) {
+        best = metric_value(*st, opt_.metric);
+        num_out_states = 0;
+      }
+      if (metric_value(*st, opt_.metric) <= best) {
+        if (num_out_states < std::min(20, opt_.beam)) {
+          out_states[num_out_states++] = *st;
+        } else if (opt_.verbosity >= 0) {
+          std::printf("Output state buffer full! Throwing away valid state.\n");
         }
       }
     };
@@ -1049,10 +1048,6 @@ void Engine::generate_graph(const state& st_in) {
       }
 
       // Collect this iteration's tasks.
-      struct Task {
-        int current;
-        u8 output;
-      };
       std::vector<Task> tasks;
       for (int current = 0; current < num_start_states; current++) {
         for (u8 output = 0; output < num_outputs_; output++) {
@@ -1066,83 +1061,21 @@ void Engine::generate_graph(const state& st_in) {
           if (opt_.verbosity >= 0) {
             std::printf("Generating circuit for output %d...\n", task.output);
           }
-          i8 bits[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-          state st = start_states[task.current];
-          if (opt_.metric == METRIC_GATES) {
-            st.max_gates = max_gates;
-          } else {
-            st.max_sat_metric = max_sat_metric;
-          }
-          const ttable mask = tt_mask_for_inputs(get_num_inputs(&st));
-          st.outputs[task.output] = create_circuit(&st, g_target_[task.output], mask, bits);
-          if (st.outputs[task.output] == NO_GATE) {
-            if (opt_.verbosity >= 0) {
-              std::printf("No solution for output %d.\n", task.output);
-            }
-            continue;
-          }
-          assert(tt_eq_mask(g_target_[task.output],
-                            st.gates[st.outputs[task.output]].table, mask));
-          save_checkpoint(st);
-          consider(st);
+          fold(task, search_output(start_of(task), task.output));
         }
       } else {
-        // Bounds for every task in this round are fixed at round start.
-        const gatenum round_max_gates = max_gates;
-        const int round_max_sat = max_sat_metric;
-        std::vector<state> results(tasks.size());
-        std::vector<char> ok(tasks.size(), 0);
-        size_t next = 0;
-        while (next < tasks.size()) {
-          const size_t batch = std::min<size_t>(opt_.jobs, tasks.size() - next);
-          std::vector<std::thread> threads;
-          for (size_t j = 0; j < batch; j++) {
-            const size_t ti = next + j;
-            threads.emplace_back([&, ti, j] {
-              const Task& task = tasks[ti];
-              options wopt = opt_;
-              wopt.jobs = 1;
-              wopt.verbosity = -1;
-              if (wopt.seeded) {
-                wopt.seed = opt_.seed + 0x51ED * (iter * 1024 + static_cast<int>(ti) + 1);
-              }
-              if (devices > 0) wopt.gpu_device = static_cast<int>(j) % devices;
-              try {
-                Engine we(wopt);
-                we.set_sbox(sbox_, num_inputs_);
-                state st = start_states[task.current];
-                if (opt_.metric == METRIC_GATES) {
-                  st.max_gates = round_max_gates;
-                } else {
-                  st.max_sat_metric = round_max_sat;
-                }
-                i8 bits[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-                const ttable mask = tt_mask_for_inputs(get_num_inputs(&st));
-                st.outputs[task.output] =
-                    we.create_circuit(&st, g_target_[task.output], mask, bits);
-                if (st.outputs[task.output] != NO_GATE) {
-                  results[ti] = st;
-                  ok[ti] = 1;
-                }
-              } catch (const std::exception& e) {
-                std::fprintf(stderr, "beam job (state %d, output %d) failed: %s\n",
-                             task.current, task.output, e.what());
-              }
-            });
-          }
-          for (auto& t : threads) t.join();
-          next += batch;
+        // `best` stands still while the jobs run: one bound for the round.
+        std::vector<Job> jobs;
+        for (int ti = 0; ti < static_cast<int>(tasks.size()); ti++) {
+          jobs.push_back({opt_.seed + 0x51ED * (iter * 1024 + ti + 1),
+                          "beam job (state " + std::to_string(tasks[ti].current) +
+                              ", output " + std::to_string(tasks[ti].output) + ")"});
         }
-        for (size_t ti = 0; ti < tasks.size(); ti++) {
-          if (!ok[ti]) {
-            if (opt_.verbosity >= 0) {
-              std::printf("No solution for output %d.\n", tasks[ti].output);
-            }
-            continue;
-          }
-          save_checkpoint(results[ti]);
-          consider(results[ti]);
-        }
+        std::vector<std::optional<state>> results(tasks.size());
+        run_jobs(jobs, [&](Engine& we, int ti) {
+          results[ti] = we.search_output(start_of(tasks[ti]), tasks[ti].output);
+        });
+        for (size_t ti = 0; ti < tasks.size(); ti++) fold(tasks[ti], results[ti]);
       }
     }
     if (num_out_states == 0) {
@@ -1155,10 +1088,10 @@ void Engine::generate_graph(const state& st_in) {
       if (opt_.metric == METRIC_GATES) {
         std::printf("Found %d state%s with %d gates.\n", num_out_states,
                     num_out_states == 1 ? "" : "s",
-                    max_gates - get_num_inputs(&out_states[0]));
+                    best - get_num_inputs(&out_states[0]));
       } else {
         std::printf("Found %d state%s with SAT metric %d.\n", num_out_states,
-                    num_out_states == 1 ? "" : "s", max_sat_metric);
+                    num_out_states == 1 ? "" : "s", best);
       }
     }
     for (int i = 0; i < num_out_states; i++) start_states[i] = out_states[i];

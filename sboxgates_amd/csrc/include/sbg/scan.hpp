@@ -51,6 +51,29 @@ struct ScanRequest {
   const Avail3Matcher* matcher = nullptr;  // k=4 scans only
 };
 
+// Exclusion mask of a request from the multiplexer input bits already used
+// on the path to this node (a list of at most 8 ended by -1).
+inline u64 excl_from_inbits(const i8* inbits) {
+  u64 excl = 0;
+  for (int i = 0; i < 8 && inbits[i] != -1; i++) {
+    if (inbits[i] < 64) excl |= 1ULL << inbits[i];
+  }
+  return excl;
+}
+
+// The request for a scan over all of st's gates. Their truth tables go into
+// `pool`, which the caller keeps alive while the request is in use.
+inline ScanRequest make_scan_request(std::vector<ttable>& pool, const state& st,
+                                     const ttable& target, const ttable& mask,
+                                     u64 seed, u64 excl = 0,
+                                     const Avail3Matcher* matcher = nullptr) {
+  pool.resize(st.num_gates);
+  for (int i = 0; i < st.num_gates; i++) pool[i] = st.gates[i].table;
+  return ScanRequest{.tables = pool.data(), .n = st.num_gates, .target = target,
+                     .mask = mask, .excl_low64 = excl, .seed = seed,
+                     .count_all = false, .matcher = matcher};
+}
+
 // 3-LUT: scan combinations [begin, end) of C(n,3).
 ScanResult cpu_scan3(const ScanRequest& rq, i64 begin, i64 end);
 

@@ -12,7 +12,9 @@
 // 100k-combination frontier cap (lut.c:291).
 #pragma once
 
+#include <functional>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -44,7 +46,7 @@ struct SearchStats {
   // Host-side phase timers for the gate-mode recursion (where the wall
   // that is NOT scan time goes; see profiles/gate_mode_service.md).
   u64 nodes = 0;              // create_circuit invocations
-  double step12_seconds = 0;  // step 1/2 existing-gate and inverse sweeps
+  double step12_seconds = 0;  // step 1/2 sweeps, nodes that end there included
   double step3_seconds = 0;   // step 3 pair loop (host)
   double step4a_seconds = 0;  // step 4a NOT-augmented pair loop (host)
 };
@@ -95,12 +97,44 @@ class Engine {
   Xorshift1024& rng() { return rng_; }
 
  private:
+  // The steps of create_circuit (1 and 2 are static in search.cpp). A step
+  // that ends the node returns the node's result, which is NO_GATE when the
+  // bounds rule the node out; an empty optional means "go on".
+  void order_gates(const state& st, gatenum* order);
+  std::optional<gatenum> step3_pairs(state* st, const ttable& target,
+                                     const ttable& mask, const gatenum* order);
+  std::optional<gatenum> step4a_not_pairs(state* st, const ttable& target,
+                                          const ttable& mask, const gatenum* order);
+  std::optional<gatenum> step4b_triples(state* st, const ttable& target,
+                                        const ttable& mask);
+  // LUT mode's steps 4: NO_GATE means "go on to step 5".
   gatenum lut_search(state* st, const ttable& target, const ttable& mask,
-                     const i8* inbits, const gatenum* gate_order);
+                     const i8* inbits);
+  gatenum step5_multiplex(state* st, const ttable& target, const ttable& mask,
+                          const i8* inbits);
+  // One multiplexer on input `bit` over sub-circuits bounded by `bound`:
+  // fills nst and returns its output gate, or NO_GATE.
+  gatenum mux_lut(const state& st, const ttable& target, const ttable& mask, int bit,
+                  gatenum bound, const i8* next_inbits, state* nst);
+  gatenum mux_and_or(const state& st, const ttable& target, const ttable& mask,
+                     int bit, gatenum bound, const i8* next_inbits, state* nst);
+
   // Symmetric distributed 5/7 search body executed by every rank.
   bool distributed_lut_body(const WorkMsg& work, u16 res[10], bool* found5);
   bool dist_scan_chunked(int k, const ScanRequest& rq, u64 chunk, u16 res[10]);
-  void generate_graph_one_output_jobs(const state& st);
+
+  // `start` (bounds set) with output `output` found and wired, or nothing.
+  std::optional<state> search_output(const state& start, int output);
+  // Runs job(worker, t) for every jobs[t] on a worker engine of its own,
+  // opt_.jobs threads at a time; after_batch(first, count) follows each join.
+  struct Job {
+    u64 seed;          // the worker's seed, when this engine is seeded
+    std::string name;  // for the message when the job throws
+  };
+  void run_jobs(const std::vector<Job>& jobs,
+                const std::function<void(Engine&, int)>& job,
+                const std::function<void(int, int)>& after_batch = nullptr);
+  void finish_iteration(int index, const std::optional<state>& found, state* st);
   void save_checkpoint(const state& st);
 
   options opt_;

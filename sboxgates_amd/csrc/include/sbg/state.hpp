@@ -53,6 +53,24 @@ inline void copy_state(state& dst, const state& src) {
               offsetof(state, gates) + sizeof(gate) * src.num_gates);
 }
 
+// A state's size under a metric, the bound the state accepts on it, and
+// lowering st's bound to the size of a state that a search found.
+inline int metric_value(const state& st, metric_t metric) {
+  return metric == METRIC_GATES ? st.num_gates : st.sat_metric;
+}
+inline int metric_bound(const state& st, metric_t metric) {
+  return metric == METRIC_GATES ? st.max_gates : st.max_sat_metric;
+}
+inline void set_metric_bound(state& st, metric_t metric, int bound) {
+  if (metric == METRIC_GATES) st.max_gates = static_cast<gatenum>(bound);
+  else st.max_sat_metric = bound;
+}
+inline void tighten_bound(state& st, const state& found, metric_t metric) {
+  if (metric_value(found, metric) < metric_bound(st, metric)) {
+    set_metric_bound(st, metric, metric_value(found, metric));
+  }
+}
+
 // SAT-metric cost model (parity: state.c:168-191). Calling with LUT aborts
 // in the reference; here it returns a sentinel the callers treat as invalid.
 int sat_metric_of(int type);

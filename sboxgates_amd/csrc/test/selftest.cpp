@@ -132,18 +132,12 @@ int main() {
       if (a == b) continue;
       add_gate(&st, XOR, a, b, METRIC_GATES);
     }
-    std::vector<ttable> pool(st.num_gates);
-    for (int i = 0; i < st.num_gates; i++) pool[i] = st.gates[i].table;
-    ttable t_outer = gen_lut_ttable(0xE8, pool[3], pool[7], pool[12]);
-    ttable target = gen_lut_ttable(0x4A, t_outer, pool[17], pool[22]);
-    ScanRequest rq;
-    rq.tables = pool.data();
-    rq.n = st.num_gates;
-    rq.target = target;
-    rq.mask = tt_ones_table();
-    rq.excl_low64 = 0;
-    rq.seed = 5;
-    rq.count_all = false;
+    ttable t_outer = gen_lut_ttable(0xE8, st.gates[3].table, st.gates[7].table,
+                                    st.gates[12].table);
+    ttable target =
+        gen_lut_ttable(0x4A, t_outer, st.gates[17].table, st.gates[22].table);
+    std::vector<ttable> pool;
+    ScanRequest rq = make_scan_request(pool, st, target, tt_ones_table(), 5);
     ScanResult r = cpu_scan5(rq, 0, n_choose_k(st.num_gates, 5));
     CHECK(r.found);
     ttable got_outer = gen_lut_ttable(static_cast<u8>(r.res[0]), pool[r.res[2]],

@@ -158,6 +158,21 @@ PYBIND11_MODULE(_core, m) {
     return py::make_tuple(gates, nots, threes);
   });
 
+  // The 256-byte pair matcher (sbg/scan.hpp) of the gates list or the
+  // NOT-augmented list of a gate set.
+  m.def("pair2_matcher", [](u32 bitfield, bool try_nots, const std::string& funs) {
+    if (funs != "gates" && funs != "not") {
+      throw std::invalid_argument("funs must be \"gates\" or \"not\"");
+    }
+    options o;
+    o.set_avail_gates(bitfield);
+    o.try_nots = try_nots;
+    o.derive_function_lists();
+    Pair2Matcher pm;
+    build_pair2_matcher(funs == "not" ? o.avail_not : o.avail_gates, &pm);
+    return py::bytes(reinterpret_cast<const char*>(pm.entry), sizeof(pm.entry));
+  }, py::arg("bitfield"), py::arg("try_nots"), py::arg("funs") = "gates");
+
   // --- combinatorics ---
   m.def("n_choose_k", &n_choose_k);
   m.def("nth_combination", [](i64 n, int num, int k) {
@@ -413,6 +428,20 @@ PYBIND11_MODULE(_core, m) {
                     [](options& o, const std::string& v) {
                       o.gpu = v == "off" ? GPU_OFF : (v == "force" ? GPU_FORCE : GPU_AUTO);
                     })
+      .def_property("gpu_pairs",
+                    [](const options& o) {
+                      return o.gpu_pairs == PAIRS_OFF
+                                 ? "off"
+                                 : (o.gpu_pairs == PAIRS_FORCE ? "force" : "auto");
+                    },
+                    [](options& o, const std::string& v) {
+                      if (v != "off" && v != "auto" && v != "force") {
+                        throw std::invalid_argument(
+                            "gpu_pairs must be \"off\", \"auto\" or \"force\"");
+                      }
+                      o.gpu_pairs = v == "off" ? PAIRS_OFF
+                                               : (v == "force" ? PAIRS_FORCE : PAIRS_AUTO);
+                    })
       .def("set_avail_gates", [](options& o, u32 bf) { o.set_avail_gates(bf); })
       .def("derive_function_lists", &options::derive_function_lists);
 
@@ -462,6 +491,8 @@ PYBIND11_MODULE(_core, m) {
         d["candidates7"] = e.stats().candidates7;
         d["gpu_scans"] = e.stats().gpu_scans;
         d["cpu_scans"] = e.stats().cpu_scans;
+        d["pair_scans_gpu"] = e.stats().pair_scans_gpu;
+        d["pair_scans_cpu"] = e.stats().pair_scans_cpu;
         d["scan_seconds3"] = e.stats().scan_seconds3;
         d["scan_seconds5"] = e.stats().scan_seconds5;
         d["scan_seconds7"] = e.stats().scan_seconds7;
@@ -471,6 +502,37 @@ PYBIND11_MODULE(_core, m) {
         d["step4a_seconds"] = e.stats().step4a_seconds;
         return d;
       })
+      .def("scan_pairs", [](Engine& e, const state& st, py::bytes target,
+                            py::bytes mask, i64 begin, i64 end,
+                            const std::string& funs, py::object order) {
+        if (funs != "gates" && funs != "not") {
+          throw std::invalid_argument("funs must be \"gates\" or \"not\"");
+        }
+        std::vector<ttable> pool;
+        ScanRequest rq = make_scan_request(pool, st, tt_from_bytes(target),
+                                           tt_from_bytes(mask), 0);
+        rq.matcher2 = e.matcher2(funs == "not");
+        std::vector<gatenum> ord;
+        if (!order.is_none()) {
+          std::vector<bool> seen(st.num_gates, false);
+          for (py::handle h : order) {
+            const i64 g = h.cast<i64>();
+            if (g < 0 || g >= st.num_gates || seen[g]) {
+              throw std::invalid_argument("order must be a permutation of the pool");
+            }
+            seen[g] = true;
+            ord.push_back(static_cast<gatenum>(g));
+          }
+          if (static_cast<int>(ord.size()) != st.num_gates) {
+            throw std::invalid_argument("order must be a permutation of the pool");
+          }
+          rq.order = ord.data();
+        }
+        ScanResult r = e.scan(2, rq, begin, end);
+        std::vector<int> res(r.res, r.res + 10);
+        return py::make_tuple(r.found, res, r.evaluated);
+      }, py::arg("state"), py::arg("target"), py::arg("mask"), py::arg("begin"),
+         py::arg("end"), py::arg("funs") = "gates", py::arg("order") = py::none())
       .def("scan_pool", [](Engine& e, int k, const state& st, py::bytes target,
                            py::bytes mask, i64 begin, i64 end, u64 seed,
                            bool count_all, u64 excl) {

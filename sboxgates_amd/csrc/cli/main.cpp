@@ -4,7 +4,7 @@
 // 895-1174): -a -c -d -g -i -l -n -o -p -s -v plus INPUT_FILE, same
 // defaults (gates = AND|OR|XOR, iterations = 1), same conflict rules
 // (-c/-d mutually exclusive, -l/-s mutually exclusive). MI355X additions:
-// --convert-hip, --seed N, --cpu / --gpu, --output-dir DIR.
+// --convert-hip, --seed N, --cpu / --gpu, --gpu-pairs, --output-dir DIR.
 //
 // Unlike the reference there is no MPI launcher: --gpus N drives N devices
 // from ONE process (one host thread + one engine per GPU, shared-memory
@@ -68,6 +68,11 @@ void print_help(const char* prog) {
       "      --seed=N                  Deterministic RNG seed.\n"
       "      --cpu                     Disable the GPU path.\n"
       "      --gpu                     Require the GPU path (fail if no device).\n"
+      "      --gpu-pairs[=auto|force]  Run the pair sweeps of steps 3 and 4a as\n"
+      "                                GPU pair scans: from the measured pool\n"
+      "                                size upward (auto, the default when the\n"
+      "                                flag has no value), or always (force).\n"
+      "                                The circuits found do not change.\n"
       "      --output-dir=DIR          Directory for XML checkpoint files.\n"
       "      --resume-dir=DIR          Write checkpoints to DIR and resume the\n"
       "                                search from the best state file already\n"
@@ -103,7 +108,7 @@ int main(int argc, char** argv) {
   opt.set_avail_gates(sbg::DEFAULT_GATE_BITFIELD);
 
   enum { OPT_HIP = 1000, OPT_SEED, OPT_CPU, OPT_GPU, OPT_OUTDIR, OPT_HELP,
-         OPT_GPUS, OPT_BEAM, OPT_JOBS, OPT_MAXG, OPT_RESUME };
+         OPT_GPUS, OPT_BEAM, OPT_JOBS, OPT_MAXG, OPT_RESUME, OPT_PAIRS };
   static const struct option long_opts[] = {
       {"available-gates", required_argument, nullptr, 'a'},
       {"convert-c", no_argument, nullptr, 'c'},
@@ -120,6 +125,7 @@ int main(int argc, char** argv) {
       {"seed", required_argument, nullptr, OPT_SEED},
       {"cpu", no_argument, nullptr, OPT_CPU},
       {"gpu", no_argument, nullptr, OPT_GPU},
+      {"gpu-pairs", optional_argument, nullptr, OPT_PAIRS},
       {"output-dir", required_argument, nullptr, OPT_OUTDIR},
       {"resume-dir", required_argument, nullptr, OPT_RESUME},
       {"gpus", required_argument, nullptr, OPT_GPUS},
@@ -176,6 +182,15 @@ int main(int argc, char** argv) {
         break;
       case OPT_CPU: opt.gpu = sbg::GPU_OFF; break;
       case OPT_GPU: opt.gpu = sbg::GPU_FORCE; break;
+      case OPT_PAIRS:
+        if (optarg == nullptr || std::strcmp(optarg, "auto") == 0) {
+          opt.gpu_pairs = sbg::PAIRS_AUTO;
+        } else if (std::strcmp(optarg, "force") == 0) {
+          opt.gpu_pairs = sbg::PAIRS_FORCE;
+        } else {
+          return fail("Bad --gpu-pairs value", optarg);
+        }
+        break;
       case OPT_OUTDIR:
         opt.output_dir = optarg;
         (void)mkdir(optarg, 0755);  // best-effort; open errors surface later
@@ -376,9 +391,11 @@ int main(int argc, char** argv) {
                   (unsigned long long)st_.gpu_scans,
                   (unsigned long long)st_.cpu_scans);
       std::printf("Host phases: %llu nodes; step1/2 %.2fs, step3 %.2fs, "
-                  "step4a %.2fs\n",
+                  "step4a %.2fs; pair scans %llu GPU / %llu CPU\n",
                   (unsigned long long)st_.nodes, st_.step12_seconds,
-                  st_.step3_seconds, st_.step4a_seconds);
+                  st_.step3_seconds, st_.step4a_seconds,
+                  (unsigned long long)st_.pair_scans_gpu,
+                  (unsigned long long)st_.pair_scans_cpu);
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "%s\n", e.what());

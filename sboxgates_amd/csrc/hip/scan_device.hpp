@@ -2,7 +2,7 @@
 // (scan_kernels.hip) and the persistent k=4 service (scan_service.hip):
 // control block, rank decoders, abort/publish, LDS staging, the
 // gate-transposed pool and its per-position cell test, the k=3/k=4 triple
-// walk and the prefix-batch layer of the k=5/k=7 scans.
+// walk, the k=2 pair walk and the prefix-batch layer of the k=5/k=7 scans.
 //
 // Everything here is __device__ __forceinline__ or has internal linkage, so
 // each .hip file is a self-contained translation unit (no relocatable
@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
@@ -48,6 +49,9 @@ struct DevCtl {
   unsigned long long hit_count;  // K7 filter
   u32 overflow;                  // K7 filter: hit buffer overflowed
   u32 pad3;
+  // k=2: minimum over the hits of rank << 8 | matcher entry. The host, or
+  // the service leader, sets it to all-ones before every request.
+  unsigned long long best;
 };
 
 struct Hit7 {
@@ -189,12 +193,40 @@ __device__ __forceinline__ void dev_publish(DevCtl* ctl, const u16 res[10]) {
   }
 }
 
+// What a k=2 request carries besides the pool: the pair matcher and the
+// visit order (order[j] < n for j < n; the tail is never read). Sized in
+// whole u64 words so that it is copied and staged 8 bytes at a time.
+struct Pair2Stage {
+  u8 matcher[256];
+  u16 order[(MAX_GATES + 3) / 4 * 4];
+};
+static_assert(sizeof(Pair2Stage) % 8 == 0);
+
+// A k=2 request must name its matcher, and its order must stay inside the
+// pool: the kernels index the LDS pool with it unchecked.
+inline void check_pair2_request(const ScanRequest& rq) {
+  if (rq.matcher2 == nullptr) throw std::runtime_error("scan2 needs matcher2");
+  if (rq.n > MAX_GATES) throw std::runtime_error("scan2: pool too large");
+  if (rq.order == nullptr) return;
+  for (int j = 0; j < rq.n; j++) {
+    if (rq.order[j] >= rq.n) throw std::runtime_error("scan2: order out of range");
+  }
+}
+
+inline void fill_pair2_stage(Pair2Stage* out, const ScanRequest& rq) {
+  std::memcpy(out->matcher, rq.matcher2->entry, sizeof(out->matcher));
+  for (int j = 0; j < rq.n; j++) {
+    out->order[j] = rq.order != nullptr ? rq.order[j] : static_cast<u16>(j);
+  }
+}
+
 struct ScanArgs {
   const ttable* pool;  // device pool (n tables)
   DevCtl* ctl;
   Hit7* hits;          // K7 only
   u64 hit_cap;         // K7 only
   const Avail3Matcher* matcher;  // k=4 only
+  const Pair2Stage* pair2;       // k=2 only
   ttable T1, T0;
   int n;
   i64 begin, end;
@@ -591,6 +623,73 @@ __device__ __forceinline__ u64 walk_triples(const u64* s_pool, int n,
     if (on_feasible(idx, a, b, c, p1, p0)) break;
   }
   return local_eval;
+}
+
+// Cooperative copy of a k=2 stage, global to global or into LDS.
+__device__ __forceinline__ void copy_pair2_stage(Pair2Stage* dst,
+                                                const Pair2Stage* src) {
+  for (int i = threadIdx.x; i < static_cast<int>(sizeof(Pair2Stage) / 8);
+       i += blockDim.x) {
+    reinterpret_cast<u64*>(dst)[i] = reinterpret_cast<const u64*>(src)[i];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Pair walk shared by the one-shot k=2 kernel and the persistent service:
+// grid-strided walk of pair ranks [idx0, end) with stride `stride` over
+// visit positions i < k, pool and Pair2Stage staged in LDS by the caller.
+// The scan's answer is the hit of the lowest rank, so a hit only lowers
+// ctl->best (rank << 8 | matcher entry) and nobody is told to stop: a
+// thread leaves once its own rank, which only grows, is past the best
+// known. No lock, no publish, no abort flag.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void walk_pairs(const u64* s_pool,
+                                           const Pair2Stage* s_pair2, int n,
+                                           const ttable& T1, const ttable& T0,
+                                           DevCtl* ctl, i64 idx0, i64 end,
+                                           i64 stride) {
+  if (n < 2) return;
+  if (end > cf2(n)) end = cf2(n);
+  int tick = 0;
+  for (i64 idx = idx0; idx < end; idx += stride) {
+    if (((tick++) & 255) == 0) {
+      const u64 best = __hip_atomic_load(as_gu64(&ctl->best), __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+      if (static_cast<u64>(idx) > (best >> 8)) break;
+    }
+    int i, k;
+    dev_decode_pair(idx, n, &i, &k);
+    const int x = s_pair2->order[i], y = s_pair2->order[k];
+    // Per cell p = vx << 1 | vy: the target-1 and the target-0 content.
+    u64 c1[4] = {0, 0, 0, 0}, c0[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const u64 tx = s_pool[x * PSTR + w], ty = s_pool[y * PSTR + w];
+      const u64 x1 = tx & T1.w[w], n1 = T1.w[w] ^ x1;
+      const u64 x0 = tx & T0.w[w], n0 = T0.w[w] ^ x0;
+      const u64 a = x1 & ty, b = n1 & ty, c = x0 & ty, d = n0 & ty;
+      c1[3] |= a;
+      c1[2] |= x1 ^ a;
+      c1[1] |= b;
+      c1[0] |= n1 ^ b;
+      c0[3] |= c;
+      c0[2] |= x0 ^ c;
+      c0[1] |= d;
+      c0[0] |= n0 ^ d;
+    }
+    u32 r1 = 0, r0 = 0;
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+      r1 |= static_cast<u32>(c1[p] != 0) << p;
+      r0 |= static_cast<u32>(c0[p] != 0) << p;
+    }
+    if ((r1 & r0) != 0) continue;  // a cell forced both ways
+    const u32 e = s_pair2->matcher[(r1 | r0) << 4 | r1];
+    if (e == PAIR2_NONE) continue;
+    __hip_atomic_fetch_min(as_gu64(&ctl->best), static_cast<u64>(idx) << 8 | e,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    break;  // this thread's later ranks are all higher
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -101,6 +101,23 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4(ScanArgs args) {
   block_add_evaluated(ctl, local_eval);
 }
 
+// K1p — gate-mode step-3/4a pair scan, one-shot launch: one thread per pair
+// rank, grid-stride, the launch shape of k_scan3. The lowest hit rank lands
+// in ctl->best (walk_pairs in scan_device.hpp); the host derives the result.
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan2(ScanArgs args) {
+  __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
+  __shared__ alignas(16) Pair2Stage s_pair2;
+  load_pool_lds(s_pool, args.pool, args.n);
+  copy_pair2_stage(&s_pair2, args.pair2);
+  __syncthreads();
+
+  const i64 stride = static_cast<i64>(gridDim.x) * blockDim.x;
+  const i64 idx0 =
+      args.begin + blockIdx.x * static_cast<i64>(blockDim.x) + threadIdx.x;
+  walk_pairs(s_pool, &s_pair2, args.n, args.T1, args.T0, args.ctl, idx0,
+             args.end, stride);
+}
+
 // ---------------------------------------------------------------------------
 // K3 — 5-LUT scan. Workgroups dequeue triple prefixes; the 8 prefix cells
 // (masked with target-1/target-0) are computed cooperatively into LDS; each
@@ -853,6 +870,8 @@ struct GpuEngine::Impl {
   DevCtl* d_ctl = nullptr;
   Hit7* d_hits = nullptr;
   Avail3Matcher* d_matcher = nullptr;
+  Pair2Stage* d_pair2 = nullptr;  // k=2: matcher and visit order
+  Pair2Stage* h_pair2 = nullptr;  // pinned staging
   ttable* h_pool = nullptr;  // pinned staging: pageable-source async
                              // copies cost ~100s of us on small scans
   const Avail3Matcher* last_matcher = nullptr;  // uploaded-matcher cache
@@ -878,6 +897,8 @@ struct GpuEngine::Impl {
     }
     if (d_pool != nullptr) (void)hipFree(d_pool);
     if (d_matcher != nullptr) (void)hipFree(d_matcher);
+    if (d_pair2 != nullptr) (void)hipFree(d_pair2);
+    if (h_pair2 != nullptr) (void)hipHostFree(h_pair2);
     if (d_ctl != nullptr) (void)hipFree(d_ctl);
     if (d_hits != nullptr) (void)hipFree(d_hits);
     if (h_ctl != nullptr) (void)hipHostFree(h_ctl);
@@ -942,6 +963,8 @@ std::unique_ptr<GpuEngine> GpuEngine::create(int device, std::string* err) {
     SBG_HIP_CHECK(hipMalloc(&impl->d_pool, sizeof(ttable) * MAX_GATES));
     SBG_HIP_CHECK(hipMalloc(&impl->d_ctl, sizeof(DevCtl)));
     SBG_HIP_CHECK(hipMalloc(&impl->d_matcher, sizeof(Avail3Matcher)));
+    SBG_HIP_CHECK(hipMalloc(&impl->d_pair2, sizeof(Pair2Stage)));
+    SBG_HIP_CHECK(hipHostMalloc(&impl->h_pair2, sizeof(Pair2Stage)));
     SBG_HIP_CHECK(hipHostMalloc(&impl->h_ctl, sizeof(DevCtl)));
     SBG_HIP_CHECK(hipHostMalloc(&impl->h_pool, sizeof(ttable) * MAX_GATES));
     // Hit buffer for the 7-LUT frontier: default 16M hits (768 MB) per
@@ -983,6 +1006,7 @@ bool GpuEngine::scan4_service_active() {
 
 ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   ScanResult out;
+  if (k == 2 && begin < 0) begin = 0;  // as cpu_scan2 does
   const i64 total = n_choose_k(rq.n, k == 4 ? 3 : k);
   if (begin >= total) return out;
   if (end > total) end = total;
@@ -994,10 +1018,14 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   // Service only for small/medium ranges: its 64-WG grid is sized for the
   // request/response round trip, not for multi-million-candidate scans —
   // those go to the one-shot kernel with a work-sized grid.
-  if (k == 4 && end - begin <= (1 << 20) && scan4_service_active()) {
-    if (rq.matcher == nullptr) throw std::runtime_error("scan4 needs matcher");
+  if (k == 2) check_pair2_request(rq);
+  if ((k == 4 || k == 2) && end - begin <= (1 << 20) && scan4_service_active()) {
+    if (k == 4 && rq.matcher == nullptr) {
+      throw std::runtime_error("scan4 needs matcher");
+    }
     try {
-      return im->svc->scan4(rq, begin, end);
+      return k == 4 ? im->svc->scan4(rq, begin, end)
+                    : im->svc->scan2(rq, begin, end);
     } catch (const std::exception& e) {
       // Service failure (residency/timeout): permanently fall back to the
       // one-shot launch path for this engine.
@@ -1005,7 +1033,7 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
       im->svc.reset();
       im->svc_broken = true;
     }
-  } else if (k != 4 && im->svc != nullptr) {
+  } else if (k != 4 && k != 2 && im->svc != nullptr) {
     // Do not let an idle-resident service delay other kernels.
     im->svc->park();
   }
@@ -1022,6 +1050,7 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   args.hits = im->d_hits;
   args.hit_cap = im->hit_cap;
   args.matcher = im->d_matcher;
+  args.pair2 = im->d_pair2;
   args.T1 = rq.target & rq.mask;
   args.T0 = ~rq.target & rq.mask;
   args.n = rq.n;
@@ -1032,7 +1061,17 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   args.count_all = rq.count_all ? 1 : 0;
   args.slices7 = 1;
 
-  if (k == 3 || k == 4) {
+  if (k == 2) {
+    fill_pair2_stage(im->h_pair2, rq);
+    SBG_HIP_CHECK(hipMemcpyAsync(im->d_pair2, im->h_pair2, sizeof(Pair2Stage),
+                                 hipMemcpyHostToDevice, im->stream));
+    im->h_ctl->best = ~0ULL;
+    const i64 range = end - begin;
+    const int grid = static_cast<int>(
+        std::min<i64>((range + SCAN_BLOCK - 1) / SCAN_BLOCK, 4096));
+    im->run(k_scan2, grid, args);
+    return pair2_result(im->h_ctl->best, rq, begin, end);
+  } else if (k == 3 || k == 4) {
     if (k == 4) {
       if (rq.matcher == nullptr) throw std::runtime_error("scan4 needs matcher");
       if (im->last_matcher != rq.matcher) {

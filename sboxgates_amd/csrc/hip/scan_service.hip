@@ -1,5 +1,6 @@
-// scan_service.hip — persistent k=4 scan service: the resident
-// k_scan4_service kernel, its mailbox protocol and the host ScanService.
+// scan_service.hip — persistent scan service: the resident k_scan4_service
+// kernel (k=4 triple scans and k=2 pair scans), its mailbox protocol and
+// the host ScanService.
 //
 // Gate-mode searches issue one step-4 triple scan per recursion node
 // (~600k nodes for AES bit 0); through the one-shot launch path each scan
@@ -51,7 +52,8 @@ enum {
   HDR_EPOCH_CALL = 1, // matcher_epoch (lo32) | count_all (hi32)
   HDR_BEGIN = 2,
   HDR_END = 3,
-                      // 4..7 reserved
+  HDR_OP = 4,         // scan kind: 4 (triples) or 2 (pairs)
+                      // 5..7 reserved
   HDR_T1 = 8,         // 8..11
   HDR_T0 = 12,        // 12..15
   HDR_WORDS = 16,
@@ -72,6 +74,7 @@ struct SvcMailbox {  // pinned fine-grained host memory
   alignas(64) u64 hdr[HDR_WORDS];
   alignas(64) ttable pool_staging[MAX_GATES];  // full pool image (host shadow)
   alignas(64) Avail3Matcher matcher_staging;
+  alignas(64) Pair2Stage pair2_staging;  // k=2: rewritten by every request
 };
 
 struct SvcDev {  // device memory
@@ -82,6 +85,7 @@ struct SvcDev {  // device memory
   alignas(64) u64 hdr[HDR_WORDS];
   alignas(64) ttable pool[MAX_GATES];
   alignas(64) Avail3Matcher matcher;
+  alignas(64) Pair2Stage pair2;
 };
 
 namespace {
@@ -100,10 +104,15 @@ inline int svc_idle_polls() {
 
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
                                                               SvcDev* dev,
-                                                              int c_idle_polls) {
+                                                              int c_idle_polls,
+                                                              u64 served0) {
   __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
   __shared__ alignas(16) u8 s_bitmap[MATCHER_BITMAP_BYTES];
   __shared__ u8 s_funs[256];
+  // A k=2 request has no use for the k=4 bitmap, which every k=4 request
+  // stages afresh: its matcher and order take the bitmap's place.
+  static_assert(sizeof(Pair2Stage) <= MATCHER_BITMAP_BYTES);
+  Pair2Stage* s_pair2 = reinterpret_cast<Pair2Stage*>(s_bitmap);
   __shared__ alignas(16) u64 s_hdr[HDR_WORDS];
   __shared__ u64 s_word;
   __shared__ int s_count;
@@ -116,8 +125,13 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
   const bool leader = blockIdx.x == 0;
   // Protocol word: (req_seq << 1) | quit. Monotonic; one word carries both
   // the sequence and the command, so publish/consume is a single-flag
-  // hand-off (Guideline 16 R2 style).
-  u64 served = 0;
+  // hand-off (Guideline 16 R2 style). A fresh kernel starts from the word
+  // of the last request the host has an answer to (dev_seq starts there
+  // too), so it does not take that request for a new one: the host does not
+  // wait for such a replay, and a leader that went on to the next request
+  // while other workgroups were still in the replay reset the counters
+  // under them (a response before the scan was done, or counts of both).
+  u64 served = served0;
 
   for (;;) {
     // ---- wait for a request (or quit) ----
@@ -203,8 +217,12 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
           __syncthreads();
           if (threadIdx.x == 0) dev->matcher_epoch = epoch;
         }
+        if (s_hdr[HDR_OP] == 2) {
+          copy_pair2_stage(&dev->pair2, &mb->pair2_staging);
+        }
         if (threadIdx.x == 0) {
           dev->done = 0;
+          dev->ctl.best = ~0ULL;
           dev->ctl.abort = 0;
           dev->ctl.lock = 0;
           dev->ctl.found = 0;
@@ -246,17 +264,30 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
       T1.w[w] = s_hdr[HDR_T1 + w];
       T0.w[w] = s_hdr[HDR_T0 + w];
     }
+    const bool pairs = s_hdr[HDR_OP] == 2;
     load_pool_lds(s_pool, dev->pool, n);
-    load_matcher_lds(s_bitmap, s_funs, &s_count, &dev->matcher);
+    if (pairs) {
+      copy_pair2_stage(s_pair2, &dev->pair2);
+    } else {
+      load_matcher_lds(s_bitmap, s_funs, &s_count, &dev->matcher);
+    }
     __syncthreads();
 
     // ---- scan ----
     const i64 stride = static_cast<i64>(gridDim.x) * blockDim.x;
     const i64 idx0 =
         begin + blockIdx.x * static_cast<i64>(blockDim.x) + threadIdx.x;
-    const u64 local_eval = walk_triples(
-        s_pool, n, T1, T0, count_all, &dev->ctl, idx0, end, stride,
-        Scan4Match{s_bitmap, s_funs, s_count, count_all, &dev->ctl});
+    u64 local_eval = 0;
+    if (pairs) {
+      walk_pairs(s_pool, s_pair2, n, T1, T0, &dev->ctl, idx0, end, stride);
+      // Every wave's fetch_min has landed before the barriers below let
+      // thread 0 take its ticket.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+      local_eval = walk_triples(
+          s_pool, n, T1, T0, count_all, &dev->ctl, idx0, end, stride,
+          Scan4Match{s_bitmap, s_funs, s_count, count_all, &dev->ctl});
+    }
 
     // ---- completion: last workgroup publishes the response ----
     // The shared reduction zeroes its LDS word itself: one more workgroup
@@ -275,14 +306,34 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
           __HIP_MEMORY_SCOPE_AGENT);
       if (d == gridDim.x - 1ULL) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        const unsigned long long ev = __hip_atomic_load(
+        unsigned long long ev = __hip_atomic_load(
             as_gu64(&dev->ctl.evaluated), __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_AGENT);
-        const u32 found = __hip_atomic_load(as_gu32(&dev->ctl.found),
-                                            __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
+        u32 found = __hip_atomic_load(as_gu32(&dev->ctl.found),
+                                      __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
         u64 rw[3] = {0, 0, 0};
-        if (found != 0) {
+        if (pairs) {
+          // The answer is the minimum: decode it into the response words
+          // (layout: cpu_scan2).
+          const i64 total = cf2(n);
+          const i64 e2 = end < total ? end : total;
+          const unsigned long long best = __hip_atomic_load(
+              as_gu64(&dev->ctl.best), __ATOMIC_RELAXED,
+              __HIP_MEMORY_SCOPE_AGENT);
+          const i64 rank = static_cast<i64>(best >> 8);
+          found = best != ~0ULL && n >= 2 && rank >= begin && rank < e2;
+          ev = e2 > begin ? static_cast<unsigned long long>(e2 - begin) : 0;
+          if (found != 0) {
+            int i, k;
+            dev_decode_pair(rank, n, &i, &k);
+            const u64 x = s_pair2->order[i], y = s_pair2->order[k];
+            const bool swapped = (best & 0x80) != 0;
+            rw[0] = (best & 0x7F) | (swapped ? 1ULL << 16 : 0) |
+                    (swapped ? y : x) << 32 | (swapped ? x : y) << 48;
+            ev = static_cast<unsigned long long>(rank - begin + 1);
+          }
+        } else if (found != 0) {
           for (int i = 0; i < 10; i++) {
             rw[i >> 2] |= static_cast<u64>(dev->ctl.res[i]) << ((i & 3) * 16);
           }
@@ -432,7 +483,9 @@ std::shared_ptr<ScanService> ScanService::acquire(int device, std::string* err) 
   return p;
 }
 
-void ScanService::ensure_running_locked() {
+// answered: the sequence number of the last request that needs no serving
+// any more; the kernel serves what the mailbox holds beyond it.
+void ScanService::ensure_running_locked(u64 answered) {
   if (running_) {
     if (__atomic_load_n(&mb_->svc_state, __ATOMIC_ACQUIRE) == SVC_RUNNING) {
       return;
@@ -442,11 +495,14 @@ void ScanService::ensure_running_locked() {
     running_ = false;
   }
   SBG_HIP_CHECK(hipMemset(d_svc_, 0, SVC_DEV_CTL_BYTES));
+  const u64 served0 = answered << 1;
+  SBG_HIP_CHECK(hipMemcpy(&d_svc_->dev_seq, &served0, sizeof(u64),
+                          hipMemcpyHostToDevice));
   mb_->quit_req = 0;
   mb_->alive = 0;
   __atomic_store_n(&mb_->svc_state, SVC_RUNNING, __ATOMIC_RELEASE);
   hipLaunchKernelGGL(k_scan4_service, dim3(grid_), dim3(SCAN_BLOCK), 0, stream_,
-                     mb_, d_svc_, svc_idle_polls());
+                     mb_, d_svc_, svc_idle_polls(), served0);
   SBG_HIP_CHECK(hipGetLastError());
   running_ = true;
   relaunches_ += 1;
@@ -495,14 +551,18 @@ void ScanService::park() {
   quit_locked();
 }
 
-ScanResult ScanService::scan4(const ScanRequest& rq, i64 begin, i64 end) {
+ScanResult ScanService::request(int op, const ScanRequest& rq, i64 begin,
+                                i64 end) {
   std::lock_guard<std::mutex> lk(mu_);
   SBG_HIP_CHECK(hipSetDevice(device_));
 
-  // Matcher delta (content compare: pointers can be reused across engine
-  // lifetimes, so identity alone is not a safe key).
-  if (std::memcmp(&mb_->matcher_staging, rq.matcher, sizeof(Avail3Matcher)) !=
-      0) {
+  if (op == 2) {
+    check_pair2_request(rq);
+    fill_pair2_stage(&mb_->pair2_staging, rq);
+  } else if (std::memcmp(&mb_->matcher_staging, rq.matcher,
+                         sizeof(Avail3Matcher)) != 0) {
+    // Matcher delta (content compare: pointers can be reused across engine
+    // lifetimes, so identity alone is not a safe key).
     std::memcpy(&mb_->matcher_staging, rq.matcher, sizeof(Avail3Matcher));
     matcher_epoch_ += 1;
   }
@@ -533,11 +593,12 @@ ScanResult ScanService::scan4(const ScanRequest& rq, i64 begin, i64 end) {
       (static_cast<u64>(rq.count_all ? 1u : 0u) << 32);
   mb_->hdr[HDR_BEGIN] = static_cast<u64>(begin);
   mb_->hdr[HDR_END] = static_cast<u64>(end);
+  mb_->hdr[HDR_OP] = static_cast<u64>(op);
   for (int w = 0; w < 4; w++) {
     mb_->hdr[HDR_T1 + w] = T1.w[w];
     mb_->hdr[HDR_T0 + w] = T0.w[w];
   }
-  ensure_running_locked();
+  ensure_running_locked(seq_);
   const u64 s = ++seq_;
   __atomic_store_n(&mb_->req_seq, s, __ATOMIC_RELEASE);
 
@@ -554,7 +615,7 @@ ScanResult ScanService::scan4(const ScanRequest& rq, i64 begin, i64 end) {
       // request is still in the mailbox and the fresh kernel serves it.
       SBG_HIP_CHECK(hipStreamSynchronize(stream_));
       running_ = false;
-      ensure_running_locked();
+      ensure_running_locked(s - 1);
     }
     const auto dt = std::chrono::steady_clock::now() - t0;
     if (svc_debug() && !reported && dt > std::chrono::seconds(1)) {

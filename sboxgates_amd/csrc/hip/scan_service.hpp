@@ -1,4 +1,4 @@
-// scan_service.hpp — host interface of the persistent k=4 scan service
+// scan_service.hpp — host interface of the persistent k=4 / k=2 scan service
 // (implementation and kernel: scan_service.hip). Private to csrc/hip.
 #pragma once
 
@@ -16,7 +16,8 @@ struct SvcMailbox;
 struct SvcDev;
 
 // ---------------------------------------------------------------------------
-// ScanService — host side of the persistent k=4 scan kernel. One instance
+// ScanService — host side of the persistent scan kernel (k=4 triple scans
+// and k=2 pair scans). One instance
 // per device per process (gate-mode engines and --jobs workers share it;
 // requests serialize on a mutex, which is correct because every request is
 // a whole-device scan anyway).
@@ -27,7 +28,14 @@ class ScanService {
   ~ScanService();
 
   // Blocking k=4 scan via the resident kernel. Thread-safe.
-  ScanResult scan4(const ScanRequest& rq, i64 begin, i64 end);
+  ScanResult scan4(const ScanRequest& rq, i64 begin, i64 end) {
+    return request(4, rq, begin, end);
+  }
+  // Blocking k=2 pair scan via the same kernel, pool shadow and delta sync;
+  // rq.matcher2 and rq.order travel with every request. Thread-safe.
+  ScanResult scan2(const ScanRequest& rq, i64 begin, i64 end) {
+    return request(2, rq, begin, end);
+  }
 
   // Retire the resident kernel if it is running (used before launching
   // other kernels so an idle service never delays them). Cheap when the
@@ -36,7 +44,8 @@ class ScanService {
 
  private:
   explicit ScanService(int device);
-  void ensure_running_locked();
+  ScanResult request(int op, const ScanRequest& rq, i64 begin, i64 end);
+  void ensure_running_locked(u64 answered);
   void quit_locked();
   bool quit_bounded();
   void escalate_abort();

@@ -273,6 +273,96 @@ ScanResult cpu_scan4(const ScanRequest& rq, i64 begin, i64 end) {
   return out;
 }
 
+// --- Gate-mode step-3/4a pair scan (k = 2) ---
+
+void build_pair2_matcher(const boolfunc* funs, Pair2Matcher* out) {
+  for (int care = 0; care < 16; care++) {
+    const u8 cares = swap_pair_patterns(static_cast<u8>(care));
+    for (int req1 = 0; req1 < 16; req1++) {
+      const u8 req1s = swap_pair_patterns(static_cast<u8>(req1));
+      u8 e = PAIR2_NONE;
+      for (int m = 0; funs[m].num_inputs != 0 && e == PAIR2_NONE; m++) {
+        const u8 fpat = fun2_pattern_table(funs[m].fun);
+        if ((fpat & care) == req1) {
+          e = static_cast<u8>(m);
+        } else if (!funs[m].ab_commutative && (fpat & cares) == req1s) {
+          e = static_cast<u8>(m | 0x80);
+        }
+      }
+      out->entry[care << 4 | req1] = e;
+    }
+  }
+}
+
+ScanResult pair2_result(u64 best, const ScanRequest& rq, i64 begin, i64 end) {
+  ScanResult out;
+  out.evaluated = static_cast<u64>(end - begin);
+  if (best == ~0ULL) return out;
+  const i64 rank = static_cast<i64>(best >> 8);
+  const u8 e = static_cast<u8>(best & 0xFF);
+  int i, k;
+  decode_pair(rank, rq.n, &i, &k);
+  const gatenum x = rq.order != nullptr ? rq.order[i] : static_cast<gatenum>(i);
+  const gatenum y = rq.order != nullptr ? rq.order[k] : static_cast<gatenum>(k);
+  const bool swapped = (e & 0x80) != 0;
+  out.found = true;
+  out.res[0] = e & 0x7F;
+  out.res[1] = swapped ? 1 : 0;
+  out.res[2] = swapped ? y : x;
+  out.res[3] = swapped ? x : y;
+  out.evaluated = static_cast<u64>(rank - begin + 1);
+  return out;
+}
+
+ScanResult cpu_scan2(const ScanRequest& rq, i64 begin, i64 end) {
+  ScanResult out;
+  const i64 total = n_choose_k(rq.n, 2);
+  if (begin < 0) begin = 0;
+  if (begin >= total) return out;
+  if (end > total) end = total;
+  if (begin >= end) return out;
+  const Pair2Matcher* M = rq.matcher2;
+
+  const ttable T1 = rq.target & rq.mask;
+  const ttable T0 = ~rq.target & rq.mask;
+
+  int i, k;
+  decode_pair(begin, rq.n, &i, &k);
+  int row = -1;
+  ttable xp, xq, xr, xs;  // row gate's masked halves, as in GateHalves
+  for (i64 rank = begin; rank < end; rank++) {
+    if (i != row) {
+      row = i;
+      const ttable& tx = rq.tables[rq.order != nullptr ? rq.order[i] : i];
+      xp = tx & T1;
+      xq = ~tx & T1;
+      xr = tx & T0;
+      xs = ~tx & T0;
+    }
+    const ttable& ty = rq.tables[rq.order != nullptr ? rq.order[k] : k];
+    // Cell p = vx << 1 | vy: target-1 side, target-0 side.
+    const ttable c1[4] = {xq & ~ty, xq & ty, xp & ~ty, xp & ty};
+    const ttable c0[4] = {xs & ~ty, xs & ty, xr & ~ty, xr & ty};
+    u8 r1 = 0, r0 = 0;
+    for (int p = 0; p < 4; p++) {
+      if (tt_any(c1[p])) r1 |= static_cast<u8>(1u << p);
+      if (tt_any(c0[p])) r0 |= static_cast<u8>(1u << p);
+    }
+    if ((r1 & r0) == 0) {
+      const u8 e = M->entry[(r1 | r0) << 4 | r1];
+      if (e != PAIR2_NONE) {
+        return pair2_result(static_cast<u64>(rank) << 8 | e, rq, begin, end);
+      }
+    }
+    if (++k == rq.n) {
+      i += 1;
+      k = i + 1;
+    }
+  }
+  out.evaluated = static_cast<u64>(end - begin);
+  return out;
+}
+
 // --- Naive oracles (fresh implementations of the reference semantics) ---
 
 bool naive_check_n_lut_possible(int num, const ttable& target, const ttable& mask,

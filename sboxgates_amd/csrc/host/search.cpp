@@ -224,20 +224,6 @@ static void fill_halves(GateHalves* out, const state* st, int n, const ttable& T
   return true;
 }
 
-// Pattern-space truth table of a 2-input function: bit p = value at
-// pattern p (the 4-bit encoding is bit-reversed; see boolfunc.hpp).
-static inline u8 fun2_pattern_table(u8 fun) {
-  u8 out = 0;
-  for (u8 p = 0; p < 4; p++) out |= static_cast<u8>(fun2_val(fun, p) << p);
-  return out;
-}
-
-// Swap the two input roles of a 4-bit pattern mask (pattern vx<<1|vy ->
-// vy<<1|vx): bits 1 and 2 exchange.
-static inline u8 swap_pair_patterns(u8 m) {
-  return static_cast<u8>((m & 0x9) | ((m & 2) << 1) | ((m & 4) >> 1));
-}
-
 // The calling thread's halves buffer. Step 3 fills it and step 4a of the same
 // node reads it, both before step 5 recurses, so one per thread is enough.
 static std::vector<GateHalves>& halves_scratch() {
@@ -323,6 +309,15 @@ const Avail3Matcher* Engine::matcher3() {
   return matcher_.get();
 }
 
+const Pair2Matcher* Engine::matcher2(bool nots) {
+  std::unique_ptr<Pair2Matcher>& m = matcher2_[nots ? 1 : 0];
+  if (m == nullptr) {
+    m = std::make_unique<Pair2Matcher>();
+    build_pair2_matcher(nots ? opt_.avail_not : opt_.avail_gates, m.get());
+  }
+  return m.get();
+}
+
 bool Engine::gpu_active() const { return gpu_ != nullptr; }
 
 void Engine::set_sbox(const u8 sbox[256], int num_inputs) {
@@ -338,7 +333,24 @@ void Engine::set_sbox(const u8 sbox[256], int num_inputs) {
   }
 }
 
+// Pair scan dispatch: on the GPU when it is forced (by gpu or by
+// gpu_pairs) or the window reaches the measured cutover. Its counters are
+// its own: the k=3/4 totals feed the adaptive k=4 cutover.
+ScanResult Engine::scan_pairs(const ScanRequest& rq, i64 begin, i64 end) {
+  if (rq.matcher2 == nullptr) throw std::runtime_error("scan2 needs matcher2");
+  const bool use_gpu =
+      gpu_ != nullptr && (opt_.gpu == GPU_FORCE || opt_.gpu_pairs == PAIRS_FORCE ||
+                          end - begin >= GPU_PAIRS_MIN);
+  if (use_gpu) {
+    stats_.pair_scans_gpu += 1;
+    return gpu_->scan(2, rq, begin, end);
+  }
+  stats_.pair_scans_cpu += 1;
+  return cpu_scan2(rq, begin, end);
+}
+
 ScanResult Engine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
+  if (k == 2) return scan_pairs(rq, begin, end);
   // Per-k GPU cutover: per-combination cost grows steeply with k (a 7-LUT
   // feasibility check walks 128 cells vs 32 for 5-LUT and 8 for 3-LUT), so
   // the range size where the GPU (incl. ~20-40us launch+upload overhead)
@@ -659,12 +671,40 @@ std::optional<gatenum> Engine::step3_pairs(state* st, const ttable& target,
   if (!check_num_gates_possible(st, 1, sat_metric_of(AND), opt_.metric)) {
     return NO_GATE;
   }
+  if (pairs_on_gpu(st->num_gates)) {
+    PhaseTimer timer{&stats_.step3_seconds};
+    return pair_scan(st, target, mask, order, false, "step3");
+  }
   std::vector<GateHalves>& halves = halves_scratch();
   halves.resize(st->num_gates);
   fill_halves(halves.data(), st, st->num_gates, target & mask, ~target & mask);
   PhaseTimer timer{&stats_.step3_seconds};
   return pair_sweep(st, target, mask, halves.data(), order, opt_.avail_gates,
                     opt_.metric, "step3");
+}
+
+// A function of n only, so steps 3 and 4a of a node decide alike: step 4a's
+// host sweep needs the halves that step 3's host sweep left.
+bool Engine::pairs_on_gpu(int n) const {
+  if (gpu_ == nullptr || opt_.gpu_pairs == PAIRS_OFF) return false;
+  return opt_.gpu_pairs == PAIRS_FORCE || n_choose_k(n, 2) >= GPU_PAIRS_MIN;
+}
+
+// The sweep as a k=2 scan in the node's visit order; the hit is the host
+// sweep's first match and is appended the same way. Draws no random numbers.
+std::optional<gatenum> Engine::pair_scan(state* st, const ttable& target,
+                                         const ttable& mask, const gatenum* order,
+                                         bool nots, const char* where) {
+  static thread_local std::vector<ttable> pool;
+  ScanRequest rq = make_scan_request(pool, *st, target, mask, 0);
+  rq.matcher2 = matcher2(nots);
+  rq.order = order;
+  const ScanResult r = scan(2, rq, 0, n_choose_k(rq.n, 2));
+  if (!r.found) return std::nullopt;
+  const boolfunc* funs = nots ? opt_.avail_not : opt_.avail_gates;
+  return assert_ret(
+      add_boolfunc_2(st, funs[r.res[0]], r.res[2], r.res[3], opt_.metric), target,
+      st, mask, where);
 }
 
 // Step 4a: pairs with NOT-augmented functions (sboxgates.c:358-386), over
@@ -682,6 +722,9 @@ std::optional<gatenum> Engine::step4a_not_pairs(state* st, const ttable& target,
   // the AES bit-0 CPU run).
   if (opt_.avail_not[0].num_inputs == 0) return std::nullopt;
   PhaseTimer timer{&stats_.step4a_seconds};
+  if (pairs_on_gpu(st->num_gates)) {
+    return pair_scan(st, target, mask, order, true, "step4a");
+  }
   return pair_sweep(st, target, mask, halves_scratch().data(), order,
                     opt_.avail_not, opt_.metric, "step4a");
 }

@@ -1,7 +1,7 @@
 // gpu.hpp — single-GPU scan engine: CDNA4 (gfx950) HIP kernels for the
-// 3/5/7-LUT candidate scans. Implementation: csrc/hip/scan_kernels.hip
-// (one-shot kernels, GpuEngine) and csrc/hip/scan_service.hip (persistent
-// k=4 service).
+// 3/5/7-LUT candidate scans and the gate-mode triple (k=4) and pair (k=2)
+// scans. Implementation: csrc/hip/scan_kernels.hip (one-shot kernels,
+// GpuEngine) and csrc/hip/scan_service.hip (persistent k=4 / k=2 service).
 //
 // One GpuEngine owns one device (HIP_VISIBLE_DEVICES / torchrun LOCAL_RANK
 // selects which): multi-GPU runs use one process per GPU with RCCL-backed
@@ -30,8 +30,11 @@ class GpuEngine {
   static std::unique_ptr<GpuEngine> create(int device, std::string* err);
   ~GpuEngine();
 
-  // Scans combinations [begin, end) of C(rq.n, k), k in {3,4,5,7}.
-  // Blocking; early-exits via an in-kernel abort flag unless rq.count_all.
+  // Scans combinations [begin, end) of C(rq.n, k), k in {2,3,4,5,7} (k=4
+  // ranks triples). Blocking; early-exits via an in-kernel abort flag
+  // unless rq.count_all. k=2 is the pair scan: it needs rq.matcher2,
+  // reports the hit of the lowest rank (see cpu_scan2) and, like k=4, goes
+  // through the scan service when that is active.
   ScanResult scan(int k, const ScanRequest& rq, i64 begin, i64 end);
 
   // True when k=4 scans go through the persistent scan-service kernel

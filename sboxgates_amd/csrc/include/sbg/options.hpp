@@ -16,6 +16,22 @@ enum gpu_mode_t : i32 {
   GPU_FORCE = 2,  // fail loudly if no GPU / kernels unavailable
 };
 
+// Where the pair sweeps of gate-mode steps 3 and 4a run on an engine that
+// has a GPU. The circuit found is the same under all three: the pair scan
+// reports the hit of the lowest rank, which is the host sweep's first match.
+enum gpu_pairs_t : i32 {
+  PAIRS_OFF = 0,    // host sweep
+  PAIRS_AUTO = 1,   // GPU pair scan from GPU_PAIRS_MIN pairs upward
+  PAIRS_FORCE = 2,  // GPU pair scan for every sweep
+};
+
+// PAIRS_AUTO cutover, in pairs C(n,2) of the node's pool: n = 170, the
+// smallest measured pool at which the scan-service round trip of a k=2
+// request (16.6 us per node) beat the host sweep of a node that misses
+// (19.8 us; at n = 140 the host still won, 13.6 us against 16.6 us). Table
+// and derivation: profiles/gate_mode_service.md.
+constexpr i64 GPU_PAIRS_MIN = 170 * 169 / 2;
+
 struct options {
   std::string fname;        // Input file (S-box table, or XML for -c/-d).
   std::string gfname;       // -g: initial graph file.
@@ -40,6 +56,7 @@ struct options {
   bool seeded = false;      // --seed given: deterministic RNG
   u64 seed = 0;
   gpu_mode_t gpu = GPU_AUTO;
+  gpu_pairs_t gpu_pairs = PAIRS_OFF;  // --gpu-pairs
   int gpu_device = -1;      // HIP device index; -1 = current device
   int num_gpus = 1;         // CLI --gpus: in-process devices (threads)
   int beam = 20;            // --beam: tied-state beam width (<= 20; the

@@ -9,6 +9,8 @@
 //   3-LUT: res[0]=func,                res[1..3]=gate ids
 //   5-LUT: res[0]=fo, res[1]=fi,       res[2..6]=gate ids (outer a,b,c; d,e)
 //   7-LUT: res[0]=fo, res[1]=fm, res[2]=fi, res[3..9]=gate ids
+// The pair scan (k=2, gate-mode steps 3 and 4a) is the exception: it
+// reports the hit of the lowest rank, see cpu_scan2.
 #pragma once
 
 #include <vector>
@@ -39,6 +41,17 @@ struct Avail3Matcher {
   int count;
 };
 
+// Precomputed matcher for the pair scan (k=2) over one 2-input function
+// list: entry[care << 4 | req1] is m | swapped << 7 for the first function m
+// of the list, in list order, that meets the 4-cell requirements directly
+// or, when it is not ab_commutative, with its arguments swapped (direct
+// before swapped, both before m + 1). PAIR2_NONE: no function does. A list
+// holds at most 48 entries.
+constexpr u8 PAIR2_NONE = 0xFF;
+struct Pair2Matcher {
+  u8 entry[256];
+};
+
 // Packed scan request shared by CPU and GPU paths.
 struct ScanRequest {
   const ttable* tables;  // gate pool truth tables, ids 0..n-1
@@ -49,6 +62,10 @@ struct ScanRequest {
   u64 seed;              // randomization source
   bool count_all;        // true: never early-exit (bench mode)
   const Avail3Matcher* matcher = nullptr;  // k=4 scans only
+  const Pair2Matcher* matcher2 = nullptr;  // k=2 scans only
+  // k=2 scans only: visit position j holds gate order[j], a permutation of
+  // the pool ids; null is the identity.
+  const gatenum* order = nullptr;
 };
 
 // Exclusion mask of a request from the multiplexer input bits already used
@@ -90,6 +107,39 @@ ScanResult cpu_scan7(const ScanRequest& rq, i64 begin, i64 end);
 // Result: res[0]=avail index, res[1]=argument order (TRIPLE_PERMS index),
 // res[2..4]=gate ids. Requires rq.matcher.
 ScanResult cpu_scan4(const ScanRequest& rq, i64 begin, i64 end);
+
+// Pair scan (k=2): walks ranks [begin, end) of C(n,2), row-major over visit
+// positions i < k, and reports the hit of the LOWEST rank in the window
+// (deterministic, unlike the other scans). With x = order[i], y = order[k]:
+// a pair whose 4-cell requirements under (target, mask) are contradictory
+// misses, otherwise rq.matcher2 names the function. res[0]=index into the
+// function list, res[1]=1 if the arguments are swapped, res[2..3]=gate ids
+// in argument order (what add_boolfunc_2 takes). evaluated = hit rank -
+// begin + 1, or the window's size on a miss. excl_low64, seed and count_all
+// have no effect. Requires rq.matcher2.
+ScanResult cpu_scan2(const ScanRequest& rq, i64 begin, i64 end);
+
+// Builds the pair matcher of a 2-input function list ended by
+// num_inputs == 0.
+void build_pair2_matcher(const boolfunc* funs, Pair2Matcher* out);
+
+// The pair scan's result from its packed minimum `best` = hit rank << 8 |
+// matcher entry, all-ones when nothing hit. [begin, end) already clipped.
+ScanResult pair2_result(u64 best, const ScanRequest& rq, i64 begin, i64 end);
+
+// Pattern-space table of a 2-input function: bit p = value at pattern
+// p = a << 1 | b (the 4-bit encoding is bit-reversed; see boolfunc.hpp).
+inline u8 fun2_pattern_table(u8 fun) {
+  u8 out = 0;
+  for (u8 p = 0; p < 4; p++) out |= static_cast<u8>(fun2_val(fun, p) << p);
+  return out;
+}
+
+// Swaps the two input roles of a 4-bit pattern mask (pattern a << 1 | b ->
+// b << 1 | a): bits 1 and 2 exchange.
+inline u8 swap_pair_patterns(u8 m) {
+  return static_cast<u8>((m & 0x9) | ((m & 2) << 1) | ((m & 4) >> 1));
+}
 
 // Builds the matcher from an avail_3-style list (funs/cost arrays).
 void build_avail3_matcher(const u8* funs, const u8* costs, int count,

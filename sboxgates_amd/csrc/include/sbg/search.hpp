@@ -35,6 +35,10 @@ struct SearchStats {
   u64 candidates7 = 0;
   u64 gpu_scans = 0;
   u64 cpu_scans = 0;
+  // Pair scans (k=2) that went through Engine::scan, by where they ran;
+  // gpu_scans / cpu_scans do not count them.
+  u64 pair_scans_gpu = 0;
+  u64 pair_scans_cpu = 0;
   double scan_seconds3 = 0;  // wall time inside 3-input scans (incl. k=4)
   double scan_seconds5 = 0;
   double scan_seconds7 = 0;
@@ -86,11 +90,15 @@ class Engine {
 
   // Scan dispatch (used by create_circuit internals, tests, and bench):
   // runs on GPU when available and the range is large enough, else CPU.
+  // k in {2,3,4,5,7}; k=2 is the pair scan (see cpu_scan2).
   ScanResult scan(int k, const ScanRequest& rq, i64 begin, i64 end);
 
   bool gpu_active() const;
   // Cached step-4 matcher built from this engine's avail_3 vocabulary.
   const Avail3Matcher* matcher3();
+  // Cached pair matcher of this engine's gates list (nots = false) or its
+  // NOT-augmented list (nots = true).
+  const Pair2Matcher* matcher2(bool nots);
   const SearchStats& stats() const { return stats_; }
   const std::vector<std::string>& saved_files() const { return saved_files_; }
   options& opt() { return opt_; }
@@ -107,6 +115,14 @@ class Engine {
                                           const ttable& mask, const gatenum* order);
   std::optional<gatenum> step4b_triples(state* st, const ttable& target,
                                         const ttable& mask);
+  // True when options::gpu_pairs sends the pair sweeps of a node with n
+  // gates through scan(2, ...).
+  bool pairs_on_gpu(int n) const;
+  // The pair sweep of step 3 (nots = false) or 4a as a k=2 scan.
+  std::optional<gatenum> pair_scan(state* st, const ttable& target,
+                                   const ttable& mask, const gatenum* order,
+                                   bool nots, const char* where);
+  ScanResult scan_pairs(const ScanRequest& rq, i64 begin, i64 end);
   // LUT mode's steps 4: NO_GATE means "go on to step 5".
   gatenum lut_search(state* st, const ttable& target, const ttable& mask,
                      const i8* inbits);
@@ -147,6 +163,7 @@ class Engine {
   ttable g_target_[8] = {};
   std::unique_ptr<GpuEngine> gpu_;
   std::unique_ptr<Avail3Matcher> matcher_;
+  std::unique_ptr<Pair2Matcher> matcher2_[2];  // gates list, NOT list
   SearchStats stats_;
   std::vector<std::string> saved_files_;
 };

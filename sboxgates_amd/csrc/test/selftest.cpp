@@ -145,6 +145,38 @@ int main() {
     ttable got = gen_lut_ttable(static_cast<u8>(r.res[1]), got_outer,
                                 pool[r.res[5]], pool[r.res[6]]);
     CHECK(tt_eq(got, target));
+
+    // Pair scan under a reversed order: a planted ANDN of two gates, in
+    // the full window and in single-rank windows up to and past the pool.
+    options popt;
+    popt.set_avail_gates(214);
+    popt.try_nots = true;
+    popt.derive_function_lists();
+    Pair2Matcher pm;
+    build_pair2_matcher(popt.avail_gates, &pm);
+    gatenum order[MAX_GATES];
+    for (int i = 0; i < st.num_gates; i++) {
+      order[i] = static_cast<gatenum>(st.num_gates - 1 - i);
+    }
+    const ttable ptarget =
+        gen_ttable_2(A_AND_NOT_B, st.gates[9].table, st.gates[21].table);
+    ScanRequest prq = make_scan_request(pool, st, ptarget, tt_ones_table(), 0);
+    prq.matcher2 = &pm;
+    prq.order = order;
+    const i64 ptotal = n_choose_k(st.num_gates, 2);
+    ScanResult pr = cpu_scan2(prq, 0, ptotal + 7);
+    CHECK(pr.found);
+    CHECK(tt_eq(gen_ttable_2(popt.avail_gates[pr.res[0]].fun, pool[pr.res[2]],
+                             pool[pr.res[3]]),
+                ptarget));
+    u64 single_hits = 0;
+    for (i64 r = 0; r < ptotal + 2; r++) {
+      const ScanResult s = cpu_scan2(prq, r, r + 1);
+      CHECK(s.evaluated == (r < ptotal ? 1u : 0u));
+      if (s.found) single_hits += 1;
+    }
+    CHECK(single_hits >= 1);
+    CHECK(cpu_scan2(prq, pr.evaluated - 1, ptotal).evaluated == 1);
   }
 
   std::printf("selftest ok\n");

@@ -26,6 +26,7 @@ from .._core import (  # noqa: F401
     naive_check_n_lut_possible,
     naive_get_lut_function,
     nth_combination,
+    pair2_matcher,
     splits5,
     tt_eq_mask,
     ttable_to_string,
@@ -35,14 +36,21 @@ from .._core import (  # noqa: F401
 def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
                 iterations=1, metric="gates", try_nots=False,
                 save_states=False, output_dir="", verbosity=-1,
-                gate_bitfield=None, ctx=None, jobs=1):
-    """Builds an Engine with the given search options."""
+                gate_bitfield=None, ctx=None, jobs=1, gpu_pairs="off"):
+    """Builds an Engine with the given search options.
+
+    gpu_pairs routes the pair sweeps of gate-mode steps 3 and 4a on an engine
+    that has a GPU: "off" keeps the host sweep, "force" sends every sweep
+    through the k=2 pair scan, "auto" does so from the measured cutover
+    upward. The circuit found is the same under all three.
+    """
     o = _core.Options()
     o.lut_graph = lut_graph
     if seed is not None:
         o.seeded = True
         o.seed = seed
     o.gpu = gpu
+    o.gpu_pairs = gpu_pairs
     o.oneoutput = oneoutput
     o.iterations = iterations
     o.jobs = jobs
@@ -68,3 +76,19 @@ def scan(engine, k, state, target, mask, begin, end, seed=0, count_all=False,
     """
     return engine.scan_pool(k, state, target, mask, begin, end, seed, count_all,
                             excl)
+
+
+def scan_pairs(engine, state, target, mask, begin, end, funs="gates",
+               order=None):
+    """Runs the pair scan (k=2) of gate-mode steps 3 and 4a over ranks
+    [begin, end) of C(n, 2), row-major over visit positions i < k.
+
+    Position j holds gate order[j] (a permutation of the pool ids; None is
+    the identity). funs picks the engine's function list: "gates", or "not"
+    for the NOT-augmented one. Unlike the other scans the result is
+    deterministic: the hit of the lowest rank in the window. Returns (found,
+    res[10], evaluated) with res[0] = index into the function list, res[1] =
+    1 if the arguments are swapped, res[2], res[3] = gate ids in argument
+    order; evaluated = hit rank - begin + 1, or the window's size on a miss.
+    """
+    return engine.scan_pairs(state, target, mask, begin, end, funs, order)

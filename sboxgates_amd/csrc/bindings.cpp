@@ -244,6 +244,21 @@ PYBIND11_MODULE(_core, m) {
     return py::make_tuple(true, static_cast<int>(fo), static_cast<int>(fi),
                           static_cast<int>(split));
   });
+  // Shared-input two-LUT solve over an ascending 4-combination's tables:
+  // None, or (fo, fi, shape).
+  m.def("lut4s_solve", [](std::vector<py::bytes> tables, py::bytes target,
+                          py::bytes mask, u64 rnd) -> py::object {
+    if (tables.size() != 4) throw std::invalid_argument("lut4s_solve takes 4 tables");
+    std::vector<ttable> tt;
+    for (auto& b : tables) tt.push_back(tt_from_bytes(b));
+    ttable T = tt_from_bytes(target), M = tt_from_bytes(mask);
+    u32 p1, p0;
+    if (!lut4_p_masks(tt.data(), T & M, ~T & M, &p1, &p0)) return py::none();
+    u8 fo, fi;
+    int shape;
+    if (!lut4s_solve_from_p(p1, p0, rnd, &fo, &fi, &shape)) return py::none();
+    return py::make_tuple(static_cast<int>(fo), static_cast<int>(fi), shape);
+  });
   m.def("lut7_solve", [](std::vector<py::bytes> tables, py::bytes target,
                          py::bytes mask, u64 rnd) -> py::tuple {
     std::vector<ttable> tt;
@@ -410,6 +425,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("oneoutput", &options::oneoutput)
       .def_readwrite("permute", &options::permute)
       .def_readwrite("lut_graph", &options::lut_graph)
+      .def_readwrite("lut_shared", &options::lut_shared)
       .def_readwrite("try_nots", &options::try_nots)
       .def_readwrite("verbosity", &options::verbosity)
       .def_readwrite("seeded", &options::seeded)
@@ -489,6 +505,8 @@ PYBIND11_MODULE(_core, m) {
         d["candidates3"] = e.stats().candidates3;
         d["candidates5"] = e.stats().candidates5;
         d["candidates7"] = e.stats().candidates7;
+        d["candidates4s"] = e.stats().candidates4s;
+        d["shared_hits"] = e.stats().shared_hits;
         d["gpu_scans"] = e.stats().gpu_scans;
         d["cpu_scans"] = e.stats().cpu_scans;
         d["pair_scans_gpu"] = e.stats().pair_scans_gpu;
@@ -496,6 +514,7 @@ PYBIND11_MODULE(_core, m) {
         d["scan_seconds3"] = e.stats().scan_seconds3;
         d["scan_seconds5"] = e.stats().scan_seconds5;
         d["scan_seconds7"] = e.stats().scan_seconds7;
+        d["scan_seconds4s"] = e.stats().scan_seconds4s;
         d["nodes"] = e.stats().nodes;
         d["step12_seconds"] = e.stats().step12_seconds;
         d["step3_seconds"] = e.stats().step3_seconds;
@@ -533,6 +552,19 @@ PYBIND11_MODULE(_core, m) {
         return py::make_tuple(r.found, res, r.evaluated);
       }, py::arg("state"), py::arg("target"), py::arg("mask"), py::arg("begin"),
          py::arg("end"), py::arg("funs") = "gates", py::arg("order") = py::none())
+      .def("scan_shared", [](Engine& e, const state& st, py::bytes target,
+                             py::bytes mask, i64 begin, i64 end, u64 seed,
+                             bool count_all, u64 excl) {
+        std::vector<ttable> pool;
+        ScanRequest rq = make_scan_request(pool, st, tt_from_bytes(target),
+                                           tt_from_bytes(mask), seed, excl);
+        rq.count_all = count_all;
+        ScanResult r = e.scan(SCAN_SHARED, rq, begin, end);
+        std::vector<int> res(r.res, r.res + 10);
+        return py::make_tuple(r.found, res, r.evaluated);
+      }, py::arg("state"), py::arg("target"), py::arg("mask"), py::arg("begin"),
+         py::arg("end"), py::arg("seed") = 0, py::arg("count_all") = false,
+         py::arg("excl") = 0)
       .def("scan_pool", [](Engine& e, int k, const state& st, py::bytes target,
                            py::bytes mask, i64 begin, i64 end, u64 seed,
                            bool count_all, u64 excl) {

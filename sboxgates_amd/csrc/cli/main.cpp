@@ -4,7 +4,8 @@
 // 895-1174): -a -c -d -g -i -l -n -o -p -s -v plus INPUT_FILE, same
 // defaults (gates = AND|OR|XOR, iterations = 1), same conflict rules
 // (-c/-d mutually exclusive, -l/-s mutually exclusive). MI355X additions:
-// --convert-hip, --seed N, --cpu / --gpu, --gpu-pairs, --output-dir DIR.
+// --convert-hip, --seed N, --cpu / --gpu, --gpu-pairs, --lut-shared,
+// --output-dir DIR.
 //
 // Unlike the reference there is no MPI launcher: --gpus N drives N devices
 // from ONE process (one host thread + one engine per GPU, shared-memory
@@ -73,6 +74,10 @@ void print_help(const char* prog) {
       "                                size upward (auto, the default when the\n"
       "                                flag has no value), or always (force).\n"
       "                                The circuits found do not change.\n"
+      "      --lut-shared              With --lut: also try two LUTs over four\n"
+      "                                gates that share an input,\n"
+      "                                LUT(LUT(x,y,z),d,s) with s one of x,y,z,\n"
+      "                                before the 5-LUT scan.\n"
       "      --output-dir=DIR          Directory for XML checkpoint files.\n"
       "      --resume-dir=DIR          Write checkpoints to DIR and resume the\n"
       "                                search from the best state file already\n"
@@ -108,7 +113,8 @@ int main(int argc, char** argv) {
   opt.set_avail_gates(sbg::DEFAULT_GATE_BITFIELD);
 
   enum { OPT_HIP = 1000, OPT_SEED, OPT_CPU, OPT_GPU, OPT_OUTDIR, OPT_HELP,
-         OPT_GPUS, OPT_BEAM, OPT_JOBS, OPT_MAXG, OPT_RESUME, OPT_PAIRS };
+         OPT_GPUS, OPT_BEAM, OPT_JOBS, OPT_MAXG, OPT_RESUME, OPT_PAIRS,
+         OPT_SHARED };
   static const struct option long_opts[] = {
       {"available-gates", required_argument, nullptr, 'a'},
       {"convert-c", no_argument, nullptr, 'c'},
@@ -126,6 +132,7 @@ int main(int argc, char** argv) {
       {"cpu", no_argument, nullptr, OPT_CPU},
       {"gpu", no_argument, nullptr, OPT_GPU},
       {"gpu-pairs", optional_argument, nullptr, OPT_PAIRS},
+      {"lut-shared", no_argument, nullptr, OPT_SHARED},
       {"output-dir", required_argument, nullptr, OPT_OUTDIR},
       {"resume-dir", required_argument, nullptr, OPT_RESUME},
       {"gpus", required_argument, nullptr, OPT_GPUS},
@@ -191,6 +198,7 @@ int main(int argc, char** argv) {
           return fail("Bad --gpu-pairs value", optarg);
         }
         break;
+      case OPT_SHARED: opt.lut_shared = true; break;
       case OPT_OUTDIR:
         opt.output_dir = optarg;
         (void)mkdir(optarg, 0755);  // best-effort; open errors surface later
@@ -235,6 +243,9 @@ int main(int argc, char** argv) {
   if (conv > 1) return fail("Cannot combine conversion options", nullptr);
   if (opt.lut_graph && opt.metric == sbg::METRIC_SAT) {
     return fail("SAT metric can not be combined with LUT graph generation", nullptr);
+  }
+  if (opt.lut_shared && !opt.lut_graph) {
+    return fail("--lut-shared can only be used with LUT graph generation", nullptr);
   }
   if (opt.fname.empty()) return fail("Input file name argument missing", nullptr);
 
@@ -390,6 +401,13 @@ int main(int argc, char** argv) {
                   rate(st_.candidates7, st_.scan_seconds7),
                   (unsigned long long)st_.gpu_scans,
                   (unsigned long long)st_.cpu_scans);
+      if (opt.lut_shared) {
+        std::printf("Shared-input scan: %llu candidates (%.3g/s), %.3fs; "
+                    "%llu hits\n",
+                    (unsigned long long)st_.candidates4s,
+                    rate(st_.candidates4s, st_.scan_seconds4s),
+                    st_.scan_seconds4s, (unsigned long long)st_.shared_hits);
+      }
       std::printf("Host phases: %llu nodes; step1/2 %.2fs, step3 %.2fs, "
                   "step4a %.2fs; pair scans %llu GPU / %llu CPU\n",
                   (unsigned long long)st_.nodes, st_.step12_seconds,

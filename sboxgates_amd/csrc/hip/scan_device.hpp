@@ -2,7 +2,8 @@
 // (scan_kernels.hip) and the persistent k=4 service (scan_service.hip):
 // control block, rank decoders, abort/publish, LDS staging, the
 // gate-transposed pool and its per-position cell test, the k=3/k=4 triple
-// walk, the k=2 pair walk and the prefix-batch layer of the k=5/k=7 scans.
+// walk, the k=2 pair walk and the prefix-batch layer of the k=5/k=7 and
+// shared-input scans.
 //
 // Everything here is __device__ __forceinline__ or has internal linkage, so
 // each .hip file is a self-contained translation unit (no relocatable
@@ -753,7 +754,8 @@ struct Scan4Match {
 };
 
 // ---------------------------------------------------------------------------
-// Prefix-batch layer of the k=5 (NP = 3) and k=7 (NP = 4) scans. A
+// Prefix-batch layer of the k=5 (NP = 3), k=7 (NP = 4) and shared-input
+// (NP = 3 of K = 4) scans. A
 // workgroup dequeues a batch of NB prefix units; NB threads decode one
 // prefix each and clip its tail window to the scan range; the 2^NP prefix
 // cells, masked with target-1 / target-0, are built cooperatively into LDS
@@ -785,9 +787,10 @@ __device__ __forceinline__ i64 dequeue_batch(DevCtl* ctl, int units,
   return batch_base;
 }
 
-// One prefix of a (2 NP - 1)-combination scan over a pool of n gates: its
-// gate ids, the flat rank `base` of its first combination, the number m of
-// gates behind its last id, and the window [lo, hi) of its C(m, NP - 1)
+// One NP-prefix of a K-combination scan over a pool of n gates (K = 2 NP - 1
+// for the k=5 and k=7 scans, K = 4 with NP = 3 for the shared-input scan):
+// its gate ids, the flat rank `base` of its first combination, the number m
+// of gates behind its last id, and the window [lo, hi) of its C(m, K - NP)
 // tail combinations that lies inside [begin, end). base < 0: no prefix.
 template <int NP>
 struct PrefixWindow {
@@ -796,10 +799,10 @@ struct PrefixWindow {
   i64 base = -1, lo = 0, hi = 0;
 };
 
-template <int NP>
+template <int NP, int K = 2 * NP - 1>
 __device__ __forceinline__ PrefixWindow<NP> decode_prefix_window(
     i64 pidx, i64 total, const ScanArgs& args) {
-  constexpr int K = 2 * NP - 1;
+  static_assert(K > NP && K - 2 >= 2);
   PrefixWindow<NP> p;
   if (pidx >= total) return p;
   const int n = args.n;
@@ -812,7 +815,8 @@ __device__ __forceinline__ PrefixWindow<NP> decode_prefix_window(
     p.base += cf<K - 3>(n - p.ids[2] - 1) - cf<K - 3>(n - p.ids[3]);
   }
   p.m = n - 1 - p.ids[NP - 1];
-  const i64 ntail = cf<NP - 1>(p.m);
+  i64 ntail;
+  if constexpr (K - NP == 1) ntail = p.m; else ntail = cf<K - NP>(p.m);
   p.lo = args.begin > p.base ? args.begin - p.base : 0;
   p.hi = args.end - p.base < ntail ? args.end - p.base : ntail;
   return p;
@@ -833,8 +837,8 @@ __device__ __forceinline__ void drop_dead_prefix(PrefixWindow<NP>& p,
   if (p.base >= args.end || p.lo >= p.hi || excl_prefix) p.lo = p.hi = 0;
 }
 
-// Cooperative prefix-cell build: NB x 2^NP cells x 4 words x {1,0} = 512
-// items at both (NP, NB) in use, two per thread. s_prefix holds the prefix
+// Cooperative prefix-cell build: NB x 2^NP cells x 4 words x {1,0} items
+// (512 for the k=5 and k=7 scans, two per thread). s_prefix holds the prefix
 // sums of the window sizes; empty windows are skipped.
 template <int NP, int NB, int STR = PSTR>
 __device__ __forceinline__ void build_prefix_cells(

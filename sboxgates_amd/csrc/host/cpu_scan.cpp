@@ -147,6 +147,94 @@ ScanResult cpu_scan5(const ScanRequest& rq, i64 begin, i64 end) {
   return out;
 }
 
+// Triple-prefix cells for the shared-input scan: the eight (a,b,c) cells,
+// intersected with T1/T0, are computed once per prefix and each d costs only
+// the final split, as PairCells does for the k=3-shaped scans.
+struct TripleCells {
+  ttable H1[8], H0[8];
+  u8 nz1 = 0, nz0 = 0;
+
+  void fill(const ttable& ta, const ttable& tb, const ttable& tc,
+            const ttable& T1, const ttable& T0) {
+    nz1 = nz0 = 0;
+    for (int u = 0; u < 8; u++) {
+      ttable pc = (u & 4 ? ta : ~ta) & (u & 2 ? tb : ~tb) & (u & 1 ? tc : ~tc);
+      H1[u] = pc & T1;
+      H0[u] = pc & T0;
+      if (tt_any(H1[u])) nz1 |= static_cast<u8>(1u << u);
+      if (tt_any(H0[u])) nz0 |= static_cast<u8>(1u << u);
+    }
+  }
+
+  // Equivalent of lut4_p_masks({ta, tb, tc, td}, ...) under this prefix.
+  bool p_masks(const ttable& td, u32* p1_out, u32* p0_out) const {
+    u32 p1 = 0, p0 = 0;
+    for (int u = 0; u < 8; u++) {
+      u32 c1 = 0, c0 = 0;  // cell bits (u<<1)|vd with content
+      if ((nz1 >> u) & 1) {
+        ttable x = H1[u] & td;
+        if (tt_any(x)) c1 |= 2;
+        if (tt_any(H1[u] ^ x)) c1 |= 1;
+      }
+      if ((nz0 >> u) & 1) {
+        ttable x = H0[u] & td;
+        if (tt_any(x)) c0 |= 2;
+        if (tt_any(H0[u] ^ x)) c0 |= 1;
+      }
+      if (c1 & c0) return false;  // a cell forced both ways
+      p1 |= c1 << (u << 1);
+      p0 |= c0 << (u << 1);
+    }
+    *p1_out = p1;
+    *p0_out = p0;
+    return true;
+  }
+};
+
+ScanResult cpu_scan4s(const ScanRequest& rq, i64 begin, i64 end) {
+  ScanResult out;
+  const i64 total = n_choose_k(rq.n, 4);
+  if (begin < 0) begin = 0;
+  if (begin >= total) return out;
+  if (end > total) end = total;
+
+  const ttable T1 = rq.target & rq.mask;
+  const ttable T0 = ~rq.target & rq.mask;
+
+  gatenum nums[4];
+  nth_combination(begin, rq.n, 4, 0, nums);
+  TripleCells tc;
+  int pa = -1, pb = -1, pc = -1;
+  for (i64 i = begin; i < end; i++) {
+    if (!excluded(rq, nums, 4)) {
+      out.evaluated++;
+      if (nums[0] != pa || nums[1] != pb || nums[2] != pc) {
+        pa = nums[0];
+        pb = nums[1];
+        pc = nums[2];
+        tc.fill(rq.tables[pa], rq.tables[pb], rq.tables[pc], T1, T0);
+      }
+      u32 p1, p0;
+      if (tc.p_masks(rq.tables[nums[3]], &p1, &p0)) {
+        u8 fo, fi;
+        int shape;
+        u64 rnd = scan_rnd(rq.seed, static_cast<u64>(i));
+        if (lut4s_solve_from_p(p1, p0, rnd, &fo, &fi, &shape) && !rq.count_all) {
+          u8 pos[5];
+          lut4s_shape_gates(shape, pos);
+          out.found = true;
+          out.res[0] = fo;
+          out.res[1] = fi;
+          for (int j = 0; j < 5; j++) out.res[2 + j] = nums[pos[j]];
+          return out;
+        }
+      }
+    }
+    next_combination(nums, 4, rq.n);
+  }
+  return out;
+}
+
 ScanResult cpu_scan7(const ScanRequest& rq, i64 begin, i64 end) {
   ScanResult out;
   const i64 total = n_choose_k(rq.n, 7);

@@ -379,10 +379,12 @@ ScanResult Engine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   const i64 gpu_min =
       k == 7 ? 256
              : (k == 5 ? 4096
-                       : (k == 4 && gpu_ != nullptr &&
-                                  gpu_->scan4_service_active()
-                              ? min4
-                              : 1 << 14));
+                       : (k == SCAN_SHARED
+                              ? GPU_SHARED_MIN
+                              : (k == 4 && gpu_ != nullptr &&
+                                         gpu_->scan4_service_active()
+                                     ? min4
+                                     : 1 << 14)));
   bool use_gpu = gpu_ != nullptr && (opt_.gpu == GPU_FORCE || end - begin >= gpu_min);
   const auto t0 = std::chrono::steady_clock::now();
   ScanResult r;
@@ -396,6 +398,7 @@ ScanResult Engine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
       case 4: r = cpu_scan4(rq, begin, end); break;
       case 5: r = cpu_scan5(rq, begin, end); break;
       case 7: r = cpu_scan7(rq, begin, end); break;
+      case SCAN_SHARED: r = cpu_scan4s(rq, begin, end); break;
       default: throw std::runtime_error("bad scan k");
     }
   }
@@ -415,14 +418,20 @@ ScanResult Engine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
       stats_.candidates5 += r.evaluated;
       stats_.scan_seconds5 += dt;
       break;
+    case SCAN_SHARED:
+      stats_.candidates4s += r.evaluated;
+      stats_.scan_seconds4s += dt;
+      break;
     default:
       stats_.candidates7 += r.evaluated;
       stats_.scan_seconds7 += dt;
       break;
   }
   if (opt_.verbosity >= 3) {
-    std::printf("[%4d] scan%d: %lld candidates in %.3fs (%.3g cand/s)%s\n",
-                ctx_->rank(), k, static_cast<long long>(r.evaluated), dt,
+    std::printf("[%4d] scan%s: %lld candidates in %.3fs (%.3g cand/s)%s\n",
+                ctx_->rank(),
+                k == SCAN_SHARED ? "4s" : std::to_string(k).c_str(),
+                static_cast<long long>(r.evaluated), dt,
                 dt > 0 ? r.evaluated / dt : 0.0, r.found ? " HIT" : "");
   }
   return r;
@@ -520,6 +529,26 @@ void Engine::stop_workers() {
   ctx_->bcast(&w, sizeof(WorkMsg), 0);
 }
 
+// Appends the two LUTs of a result in the 5-LUT layout (a 5-LUT hit or a
+// shared-input hit): res[0]=fo over gates res[2..4], res[1]=fi over that
+// LUT and gates res[5], res[6].
+static gatenum add_lut_pair(state* st, const u16 res[10], const ttable& target,
+                            const ttable& mask, const char* where) {
+  const u8 fo = static_cast<u8>(res[0]);
+  const u8 fi = static_cast<u8>(res[1]);
+  const ttable ta = st->gates[res[2]].table;
+  const ttable tb = st->gates[res[3]].table;
+  const ttable tc = st->gates[res[4]].table;
+  const ttable td = st->gates[res[5]].table;
+  const ttable te = st->gates[res[6]].table;
+  ttable t_outer = gen_lut_ttable(fo, ta, tb, tc);
+  ttable t_inner = gen_lut_ttable(fi, t_outer, td, te);
+  return assert_ret(
+      add_lut(st, fi, t_inner, add_lut(st, fo, t_outer, res[2], res[3], res[4]),
+              res[5], res[6]),
+      target, st, mask, where);
+}
+
 gatenum Engine::lut_search(state* st, const ttable& target, const ttable& mask,
                            const i8* inbits) {
   // --- 3-LUT scan (local to rank 0; parity: lut.c:501-523). ---
@@ -541,6 +570,25 @@ gatenum Engine::lut_search(state* st, const ttable& target, const ttable& mask,
 
   if (!check_num_gates_possible(st, 2, 0, opt_.metric)) return NO_GATE;
 
+  // --- Shared-input two-LUT scan (options::lut_shared; local to rank 0):
+  // LUT(LUT(x,y,z), d, s) with s one of x, y, z, over all of C(n,4). Costs
+  // the two LUTs of a 5-LUT hit and is assembled like one. ---
+  if (opt_.lut_shared && st->num_gates >= 4) {
+    static thread_local std::vector<ttable> pool;
+    const ScanRequest rq = make_scan_request(pool, *st, target, mask, rng_.next(),
+                                             excl_from_inbits(inbits));
+    ScanResult r = scan(SCAN_SHARED, rq, 0, n_choose_k(rq.n, 4));
+    if (r.found) {
+      stats_.shared_hits += 1;
+      if (opt_.verbosity >= 1) {
+        std::printf("[%4d]   Selected 4LUT-shared: %02x %02x    %3d %3d %3d %3d %3d\n",
+                    ctx_->rank(), r.res[0], r.res[1], r.res[2], r.res[3], r.res[4],
+                    r.res[5], r.res[6]);
+      }
+      return add_lut_pair(st, r.res, target, mask, "lut_search/4s");
+    }
+  }
+
   // --- Distributed 5/7-LUT search (parity: lut.c:525-631). ---
   WorkMsg w;
   std::memset(&w, 0, sizeof(w));
@@ -557,23 +605,12 @@ gatenum Engine::lut_search(state* st, const ttable& target, const ttable& mask,
   bool found5 = false;
   bool found = distributed_lut_body(w, res, &found5);
   if (found && found5) {
-    u8 fo = static_cast<u8>(res[0]);
-    u8 fi = static_cast<u8>(res[1]);
-    const ttable ta = st->gates[res[2]].table;
-    const ttable tb = st->gates[res[3]].table;
-    const ttable tc = st->gates[res[4]].table;
-    const ttable td = st->gates[res[5]].table;
-    const ttable te = st->gates[res[6]].table;
     if (opt_.verbosity >= 1) {
       std::printf("[%4d]   Selected 5LUT: %02x %02x    %3d %3d %3d %3d %3d\n",
-                  ctx_->rank(), fo, fi, res[2], res[3], res[4], res[5], res[6]);
+                  ctx_->rank(), res[0], res[1], res[2], res[3], res[4], res[5],
+                  res[6]);
     }
-    ttable t_outer = gen_lut_ttable(fo, ta, tb, tc);
-    ttable t_inner = gen_lut_ttable(fi, t_outer, td, te);
-    return assert_ret(
-        add_lut(st, fi, t_inner, add_lut(st, fo, t_outer, res[2], res[3], res[4]),
-                res[5], res[6]),
-        target, st, mask, "lut_search/5");
+    return add_lut_pair(st, res, target, mask, "lut_search/5");
   }
   if (found) {
     u8 fo = static_cast<u8>(res[0]);

@@ -1,6 +1,6 @@
 // gpu.hpp — single-GPU scan engine: CDNA4 (gfx950) HIP kernels for the
-// 3/5/7-LUT candidate scans and the gate-mode triple (k=4) and pair (k=2)
-// scans. Implementation: csrc/hip/scan_kernels.hip (one-shot kernels,
+// 3/5/7-LUT and shared-input two-LUT candidate scans and the gate-mode
+// triple (k=4) and pair (k=2) scans. Implementation: csrc/hip/scan_kernels.hip (one-shot kernels,
 // GpuEngine) and csrc/hip/scan_service.hip (persistent k=4 / k=2 service).
 //
 // One GpuEngine owns one device (HIP_VISIBLE_DEVICES / torchrun LOCAL_RANK
@@ -31,7 +31,8 @@ class GpuEngine {
   ~GpuEngine();
 
   // Scans combinations [begin, end) of C(rq.n, k), k in {2,3,4,5,7} (k=4
-  // ranks triples). Blocking; early-exits via an in-kernel abort flag
+  // ranks triples), or of C(rq.n, 4) for k = SCAN_SHARED (one-shot kernel
+  // k_scan4s, never the scan service). Blocking; early-exits via an in-kernel abort flag
   // unless rq.count_all. k=2 is the pair scan: it needs rq.matcher2,
   // reports the hit of the lowest rank (see cpu_scan2) and, like k=4, goes
   // through the scan service when that is active.

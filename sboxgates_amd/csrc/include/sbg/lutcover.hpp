@@ -101,6 +101,24 @@ SBG_HD inline bool lut7_p_masks(const ttable* t, const ttable& T1, const ttable&
   return true;
 }
 
+// k=4 over tables t[0..3]; cell bit 3 = t0's value, ..., bit 0 = t3's value.
+SBG_HD inline bool lut4_p_masks(const ttable* t, const ttable& T1, const ttable& T0,
+                                u32* p1_out, u32* p0_out) {
+  u32 p1 = 0, p0 = 0;
+  for (int c = 0; c < 16; c++) {
+    ttable cell = (c & 8 ? t[0] : ~t[0]) & (c & 4 ? t[1] : ~t[1]) &
+                  (c & 2 ? t[2] : ~t[2]) & (c & 1 ? t[3] : ~t[3]);
+    bool has1 = tt_any(cell & T1);
+    bool has0 = tt_any(cell & T0);
+    if (has1 && has0) return false;
+    if (has1) p1 |= 1u << c;
+    if (has0) p0 |= 1u << c;
+  }
+  *p1_out = p1;
+  *p0_out = p0;
+  return true;
+}
+
 // 3-LUT function from cell masks: forced-1 bits, don't-cares randomized.
 // Guarantees a NONZERO byte whenever any don't-care exists: function 00
 // does not round-trip through the gates.xsd loader (the reference's own
@@ -161,6 +179,60 @@ SBG_HD inline bool two_color_8(const u8 adj[8], u64 rnd, u8* coloring_out) {
 }
 
 // ---------------------------------------------------------------------------
+// Two-LUT solve over layer masks, shared by the 5-LUT splits and the
+// shared-input shapes: A1[v] bit u = "outer-triple cell u holds masked
+// target-1 content in layer v" (v = the inner LUT's other two inputs),
+// likewise A0. Finds an outer function fo (a proper 2-coloring of the
+// conflict graph) and the inner function fi over (o, v), pattern o<<2 | v.
+// False when the graph is not bipartite or fi is forced identically 0.
+// ---------------------------------------------------------------------------
+SBG_HD inline bool lut_solve_layers(const u8 A1[4], const u8 A0[4], u64 rnd,
+                                    u8* fo_out, u8* fi_out) {
+  // Conflict graph: u and u' must differ if some layer v has p1 at u and
+  // p0 at u' (or vice versa).
+  u8 adj[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int v = 0; v < 4; v++) {
+    for (int u = 0; u < 8; u++) {
+      u8 m = 0;
+      if ((A1[v] >> u) & 1) m |= A0[v];
+      if ((A0[v] >> u) & 1) m |= A1[v];
+      adj[u] |= m;
+    }
+  }
+  for (int u = 0; u < 8; u++) adj[u] &= static_cast<u8>(~(1u << u));
+  u8 fo;
+  if (!two_color_8(adj, rnd, &fo)) return false;
+  // function 00 does not round-trip (see lut3_function_from_p): the
+  // complement of a proper coloring is proper, so an all-zero outer
+  // byte can always be flipped.
+  if (fo == 0) fo = 0xff;
+  // Inner function over cells (o, v): inner pattern = o<<2 | v.
+  u8 fi = 0, forced = 0;
+  for (int v = 0; v < 4; v++) {
+    u8 sel1 = fo;                      // cells colored 1
+    u8 sel0 = static_cast<u8>(~fo);    // cells colored 0
+    // o = 1 class:
+    if (A1[v] & sel1) { fi |= 1u << (4 | v); forced |= 1u << (4 | v); }
+    if (A0[v] & sel1) { forced |= 1u << (4 | v); }
+    // o = 0 class:
+    if (A1[v] & sel0) { fi |= 1u << v; forced |= 1u << v; }
+    if (A0[v] & sel0) { forced |= 1u << v; }
+  }
+  fi |= static_cast<u8>(~forced) & static_cast<u8>(rnd >> 24);
+  if (fi == 0) {
+    if (forced != 0xff) {
+      u8 dc = static_cast<u8>(~forced);
+      fi = static_cast<u8>(dc & (-dc));
+    } else {
+      return false;  // inner forced identically 0: degenerate
+    }
+  }
+  *fo_out = fo;
+  *fi_out = fi;
+  return true;
+}
+
+// ---------------------------------------------------------------------------
 // 5-LUT decomposition solve. Given p1/p0 over the 32 cells (no
 // contradictions), finds a split s (0..9: which 3 of the 5 inputs feed the
 // outer LUT), an outer function fo and an inner function fi such that
@@ -191,48 +263,64 @@ SBG_HD inline bool lut5_solve_from_p(u32 p1, u32 p0, u64 rnd, u8* fo_out,
       if ((p1 >> c) & 1) A1[v] |= 1u << u;
       if ((p0 >> c) & 1) A0[v] |= 1u << u;
     }
-    // Conflict graph: u and u' must differ if some layer v has p1 at u and
-    // p0 at u' (or vice versa).
-    u8 adj[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int v = 0; v < 4; v++) {
-      for (int u = 0; u < 8; u++) {
-        u8 m = 0;
-        if ((A1[v] >> u) & 1) m |= A0[v];
-        if ((A0[v] >> u) & 1) m |= A1[v];
-        adj[u] |= m;
-      }
-    }
-    for (int u = 0; u < 8; u++) adj[u] &= static_cast<u8>(~(1u << u));
-    u8 fo;
-    if (!two_color_8(adj, rnd, &fo)) continue;
-    // function 00 does not round-trip (see lut3_function_from_p): the
-    // complement of a proper coloring is proper, so an all-zero outer
-    // byte can always be flipped.
-    if (fo == 0) fo = 0xff;
-    // Inner function over cells (o, v): inner pattern = o<<2 | v.
-    u8 fi = 0, forced = 0;
-    for (int v = 0; v < 4; v++) {
-      u8 sel1 = fo;                      // cells colored 1
-      u8 sel0 = static_cast<u8>(~fo);    // cells colored 0
-      // o = 1 class:
-      if (A1[v] & sel1) { fi |= 1u << (4 | v); forced |= 1u << (4 | v); }
-      if (A0[v] & sel1) { forced |= 1u << (4 | v); }
-      // o = 0 class:
-      if (A1[v] & sel0) { fi |= 1u << v; forced |= 1u << v; }
-      if (A0[v] & sel0) { forced |= 1u << v; }
-    }
-    fi |= static_cast<u8>(~forced) & static_cast<u8>(rnd >> 24);
-    if (fi == 0) {
-      if (forced != 0xff) {
-        u8 dc = static_cast<u8>(~forced);
-        fi = static_cast<u8>(dc & (-dc));
-      } else {
-        continue;  // inner forced identically 0: degenerate, try next split
-      }
-    }
+    u8 fo, fi;
+    if (!lut_solve_layers(A1, A0, rnd, &fo, &fi)) continue;
     *fo_out = fo;
     *fi_out = fi;
     *split_out = s;
+    return true;
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------
+// Shared-input two-LUT solve over four gates: LUT(fi; LUT(fo; x,y,z), d, s)
+// with s one of x, y, z. p1/p0 are the 16-cell masks of an ascending
+// 4-combination (lut4_p_masks, no contradictions). Shape = 3*r + si: r is
+// the position of the rest gate d in the combination, the other three
+// (ascending) are the outer triple, and si is the position of the shared
+// gate inside that triple. Seen from s, each cofactor is an arbitrary
+// g'(h'(.,.), d): the conflict graph falls apart into the s=0 and the s=1
+// triple cells, because a cell whose triple side and layer side disagree on
+// s does not exist. Shapes are tried in ascending order; outside the
+// reference's search space (its two-LUT scan takes five distinct gates).
+// ---------------------------------------------------------------------------
+constexpr int LUT4S_NUM_SHAPES = 12;
+
+// Positions, in the combination, of shape's outer triple (ascending), rest
+// gate and shared gate: the 5-LUT result order res[2..6].
+SBG_HD inline void lut4s_shape_gates(int shape, u8 pos[5]) {
+  const int r = shape / 3, si = shape - 3 * r;
+  for (int j = 0, k = 0; j < 4; j++) {
+    if (j != r) pos[k++] = static_cast<u8>(j);
+  }
+  pos[3] = static_cast<u8>(r);
+  pos[4] = pos[si];
+}
+
+SBG_HD inline bool lut4s_solve_from_p(u32 p1, u32 p0, u64 rnd, u8* fo_out,
+                                      u8* fi_out, int* shape_out) {
+  for (int shape = 0; shape < LUT4S_NUM_SHAPES; shape++) {
+    u8 pos[5];
+    lut4s_shape_gates(shape, pos);
+    const int si = shape % 3;
+    // Layer v = d<<1 | s; A1[v] bit u = p1 of the 4-cell with triple
+    // pattern u and rest value d (s is bit 2 - si of u).
+    u8 A1[4] = {0, 0, 0, 0};
+    u8 A0[4] = {0, 0, 0, 0};
+    for (int c = 0; c < 16; c++) {
+      if (!((p1 >> c) & 1) && !((p0 >> c) & 1)) continue;
+      int u = (((c >> (3 - pos[0])) & 1) << 2) | (((c >> (3 - pos[1])) & 1) << 1) |
+              ((c >> (3 - pos[2])) & 1);
+      int v = (((c >> (3 - pos[3])) & 1) << 1) | ((u >> (2 - si)) & 1);
+      if ((p1 >> c) & 1) A1[v] |= 1u << u;
+      if ((p0 >> c) & 1) A0[v] |= 1u << u;
+    }
+    u8 fo, fi;
+    if (!lut_solve_layers(A1, A0, rnd, &fo, &fi)) continue;
+    *fo_out = fo;
+    *fi_out = fi;
+    *shape_out = shape;
     return true;
   }
   return false;

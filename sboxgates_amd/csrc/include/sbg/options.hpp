@@ -32,6 +32,17 @@ enum gpu_pairs_t : i32 {
 // and derivation: profiles/gate_mode_service.md.
 constexpr i64 GPU_PAIRS_MIN = 170 * 169 / 2;
 
+// CPU/GPU cutover of the shared-input two-LUT scan (options::lut_shared), in
+// combinations C(n,4) of the window: C(21,4). A whole-range one-shot k_scan4s
+// launch costs 32-90 us up to 28 gates; cpu_scan4s crosses it between 16 and
+// 20 gates under a full mask (18.8 us against 32.2 us at 16 gates, 44.0 us
+// against 32.6 us at 20) and between 20 and 28 gates under a sparse one
+// (52 us against 90 us at 20, 338 us against 56 us at 28; interpolated about
+// 6,000 combinations). The sparse crossing is the one taken: the nodes that
+// reach this scan deep in the recursion carry sparse masks. Table:
+// profiles/lut_shared_scan.md.
+constexpr i64 GPU_SHARED_MIN = 21 * 20 * 19 * 18 / 24;
+
 struct options {
   std::string fname;        // Input file (S-box table, or XML for -c/-d).
   std::string gfname;       // -g: initial graph file.
@@ -57,6 +68,9 @@ struct options {
   u64 seed = 0;
   gpu_mode_t gpu = GPU_AUTO;
   gpu_pairs_t gpu_pairs = PAIRS_OFF;  // --gpu-pairs
+  bool lut_shared = false;  // --lut-shared: LUT mode also tries two LUTs that
+                            // share an input, LUT(LUT(x,y,z), d, s) with s
+                            // one of x, y, z, before the 5-LUT scan
   int gpu_device = -1;      // HIP device index; -1 = current device
   int num_gpus = 1;         // CLI --gpus: in-process devices (threads)
   int beam = 20;            // --beam: tied-state beam width (<= 20; the

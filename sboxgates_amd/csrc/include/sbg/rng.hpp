@@ -73,6 +73,8 @@ SBG_HD inline u64 hash_mix64(u64 z) {
 // scan draws which word (a given (seed, combination) yields the same result
 // on either engine wherever both engines use the same one):
 //  * 5-LUT: scan_rnd(seed, rank), in k_scan5 and cpu_scan5 alike.
+//  * shared-input two-LUT: scan_rnd(seed, rank), in k_scan4s and cpu_scan4s
+//    alike.
 //  * 3-LUT: hash_mix64(seed ^ rank), in k_scan3 and cpu_scan3 alike.
 //  * 7-LUT: cpu_scan7 draws hash_mix64(seed ^ rank) once per combination;
 //    k_scan7_assign draws scan_rnd(seed, hit * orderings + ordering) per

@@ -9,12 +9,15 @@
 //   3-LUT: res[0]=func,                res[1..3]=gate ids
 //   5-LUT: res[0]=fo, res[1]=fi,       res[2..6]=gate ids (outer a,b,c; d,e)
 //   7-LUT: res[0]=fo, res[1]=fm, res[2]=fi, res[3..9]=gate ids
+// The shared-input two-LUT scan (SCAN_SHARED) reports in the 5-LUT layout,
+// with res[6] equal to one of res[2..4].
 // The pair scan (k=2, gate-mode steps 3 and 4a) is the exception: it
 // reports the hit of the lowest rank, see cpu_scan2.
 #pragma once
 
 #include <vector>
 
+#include "sbg/comb.hpp"
 #include "sbg/common.hpp"
 #include "sbg/state.hpp"
 #include "sbg/ttable.hpp"
@@ -96,6 +99,23 @@ ScanResult cpu_scan3(const ScanRequest& rq, i64 begin, i64 end);
 
 // 5-LUT: scan combinations [begin, end) of C(n,5).
 ScanResult cpu_scan5(const ScanRequest& rq, i64 begin, i64 end);
+
+// Scan kind of the shared-input two-LUT scan for Engine::scan and
+// GpuEngine::scan. Not 4: that is the gate-mode triple scan.
+constexpr int SCAN_SHARED = 40;
+
+// Size of the combination space a scan kind ranks: C(n,3) for the gate-mode
+// triple scan, C(n,4) for the shared-input scan, else C(n,k).
+inline i64 scan_space(int n, int k) {
+  return n_choose_k(n, k == 4 ? 3 : (k == SCAN_SHARED ? 4 : k));
+}
+
+// Shared-input two-LUT scan: combinations [begin, end) of C(n,4), each
+// tried as LUT(LUT(x,y,z), d, s) with s one of x, y, z in the 12 shapes of
+// lut4s_solve_from_p. Result in the 5-LUT layout: res[0]=fo, res[1]=fi,
+// res[2..4]=outer triple (ascending), res[5]=rest gate d, res[6]=shared gate
+// (one of res[2..4]). Honours excl_low64 and count_all as cpu_scan5 does.
+ScanResult cpu_scan4s(const ScanRequest& rq, i64 begin, i64 end);
 
 // 7-LUT: scan combinations [begin, end) of C(n,7); feasibility filter and
 // (3,3,1) function assignment are fused per-range (no global frontier cap,

@@ -1,5 +1,6 @@
 // search.hpp — the search engine: Kwan's iterative gate-addition algorithm
-// (steps 1-5), the LUT search (3-LUT scan + distributed 5/7-LUT scans),
+// (steps 1-5), the LUT search (3-LUT scan, optional shared-input two-LUT
+// scan, distributed 5/7-LUT scans),
 // and the multi-output beam-search driver.
 //
 // Behavioral parity: sboxgates.c:280-788 and lut.c:489-631 in the
@@ -9,7 +10,9 @@
 // which can never match when the mask is partial); step-4 triples try all
 // 6 argument orders (the reference tries 4, gated on mis-indexed
 // commutativity flags, sboxgates.c:411-425); the 7-LUT search has no
-// 100k-combination frontier cap (lut.c:291).
+// 100k-combination frontier cap (lut.c:291); with options::lut_shared the
+// LUT search also tries two LUTs over four gates that share an input, a
+// shape the reference never tries.
 #pragma once
 
 #include <functional>
@@ -33,6 +36,8 @@ struct SearchStats {
   u64 candidates3 = 0;
   u64 candidates5 = 0;
   u64 candidates7 = 0;
+  u64 candidates4s = 0;  // shared-input two-LUT scan (options::lut_shared)
+  u64 shared_hits = 0;   // nodes that the shared-input scan resolved
   u64 gpu_scans = 0;
   u64 cpu_scans = 0;
   // Pair scans (k=2) that went through Engine::scan, by where they ran;
@@ -42,6 +47,7 @@ struct SearchStats {
   double scan_seconds3 = 0;  // wall time inside 3-input scans (incl. k=4)
   double scan_seconds5 = 0;
   double scan_seconds7 = 0;
+  double scan_seconds4s = 0;
   // CPU-path-only k=3/4 totals: feed the adaptive GPU cutover (the CPU
   // rate swings ~10x between full and sparse masks, so the size threshold
   // where the scan-service round trip wins moves with it).
@@ -90,7 +96,8 @@ class Engine {
 
   // Scan dispatch (used by create_circuit internals, tests, and bench):
   // runs on GPU when available and the range is large enough, else CPU.
-  // k in {2,3,4,5,7}; k=2 is the pair scan (see cpu_scan2).
+  // k in {2,3,4,5,7,SCAN_SHARED}; k=2 is the pair scan (see cpu_scan2),
+  // SCAN_SHARED the shared-input two-LUT scan (see cpu_scan4s).
   ScanResult scan(int k, const ScanRequest& rq, i64 begin, i64 end);
 
   bool gpu_active() const;

@@ -146,6 +146,27 @@ int main() {
                                 pool[r.res[5]], pool[r.res[6]]);
     CHECK(tt_eq(got, target));
 
+    // Shared-input scan: the same outer LUT with gate 3 fed to the inner
+    // LUT again, in the full window (past the space) and with the planted
+    // combination's first gate excluded.
+    const ttable starget =
+        gen_lut_ttable(0x4A, t_outer, st.gates[17].table, st.gates[3].table);
+    ScanRequest srq = make_scan_request(pool, st, starget, tt_ones_table(), 5);
+    const i64 stotal = n_choose_k(st.num_gates, 4);
+    ScanResult sr = cpu_scan4s(srq, 0, stotal + 7);
+    CHECK(sr.found);
+    CHECK(sr.res[6] == sr.res[2] || sr.res[6] == sr.res[3] || sr.res[6] == sr.res[4]);
+    got_outer = gen_lut_ttable(static_cast<u8>(sr.res[0]), pool[sr.res[2]],
+                               pool[sr.res[3]], pool[sr.res[4]]);
+    CHECK(tt_eq(gen_lut_ttable(static_cast<u8>(sr.res[1]), got_outer,
+                               pool[sr.res[5]], pool[sr.res[6]]),
+                starget));
+    srq.count_all = true;
+    CHECK(cpu_scan4s(srq, 0, stotal).evaluated == static_cast<u64>(stotal));
+    srq.excl_low64 = 1ULL << 3;
+    CHECK(cpu_scan4s(srq, 0, stotal).evaluated ==
+          static_cast<u64>(n_choose_k(st.num_gates - 1, 4)));
+
     // Pair scan under a reversed order: a planted ANDN of two gates, in
     // the full window and in single-rank windows up to and past the pool.
     options popt;

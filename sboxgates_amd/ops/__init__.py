@@ -17,6 +17,7 @@ from .._core import (  # noqa: F401
     generate_target,
     graph_to_dot,
     graph_to_source,
+    lut4s_solve,
     lut5_solve,
     lut7_ordering,
     lut7_solve,
@@ -36,14 +37,22 @@ from .._core import (  # noqa: F401
 def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
                 iterations=1, metric="gates", try_nots=False,
                 save_states=False, output_dir="", verbosity=-1,
-                gate_bitfield=None, ctx=None, jobs=1, gpu_pairs="off"):
+                gate_bitfield=None, ctx=None, jobs=1, gpu_pairs="off",
+                lut_shared=False):
     """Builds an Engine with the given search options.
 
     gpu_pairs routes the pair sweeps of gate-mode steps 3 and 4a on an engine
     that has a GPU: "off" keeps the host sweep, "force" sends every sweep
     through the k=2 pair scan, "auto" does so from the measured cutover
     upward. The circuit found is the same under all three.
+
+    lut_shared (LUT mode only) adds the shared-input two-LUT scan between the
+    3-LUT and the 5-LUT scan of every node: two LUTs over four gates,
+    LUT(LUT(x, y, z), d, s) with s one of x, y, z. Off, the search is
+    exactly what it was without the option.
     """
+    if lut_shared and not lut_graph:
+        raise ValueError("lut_shared needs lut_graph")
     o = _core.Options()
     o.lut_graph = lut_graph
     if seed is not None:
@@ -51,6 +60,7 @@ def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
         o.seed = seed
     o.gpu = gpu
     o.gpu_pairs = gpu_pairs
+    o.lut_shared = lut_shared
     o.oneoutput = oneoutput
     o.iterations = iterations
     o.jobs = jobs
@@ -76,6 +86,20 @@ def scan(engine, k, state, target, mask, begin, end, seed=0, count_all=False,
     """
     return engine.scan_pool(k, state, target, mask, begin, end, seed, count_all,
                             excl)
+
+
+def scan_shared(engine, state, target, mask, begin, end, seed=0,
+                count_all=False, excl=0):
+    """Runs the shared-input two-LUT scan over ranks [begin, end) of C(n, 4).
+
+    A 4-combination hits when LUT(fi; LUT(fo; x, y, z), d, s), with s one of
+    x, y, z, realises the target under the mask. Returns (found, res[10],
+    evaluated) in the 5-LUT layout: res[0] = fo, res[1] = fi, res[2:5] = the
+    outer triple (ascending), res[5] = the rest gate d, res[6] = the shared
+    gate, one of res[2:5]. excl and count_all as in scan().
+    """
+    return engine.scan_shared(state, target, mask, begin, end, seed, count_all,
+                              excl)
 
 
 def scan_pairs(engine, state, target, mask, begin, end, funs="gates",

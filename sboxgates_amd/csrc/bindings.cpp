@@ -283,6 +283,38 @@ PYBIND11_MODULE(_core, m) {
     }
     return py::make_tuple(false, py::object(py::none()));
   });
+  // One ordering of the 7-LUT solve, over middle functions
+  // [fm_offset, fm_offset + fm_count) of the sweep that rnd shuffles:
+  // (found, fo, fm, fi).
+  m.def("lut7_solve_ordering", [](std::vector<py::bytes> tables, py::bytes target,
+                                  py::bytes mask, int ordering_idx, u64 rnd,
+                                  int fm_offset, int fm_count) {
+    if (tables.size() != 7) {
+      throw std::invalid_argument("lut7_solve_ordering takes 7 tables");
+    }
+    if (ordering_idx < 0 || ordering_idx >= LUT7_NUM_ORDERINGS || fm_offset < 0 ||
+        fm_count < 0 || fm_offset + fm_count > 256) {
+      throw std::invalid_argument("lut7_solve_ordering: index out of range");
+    }
+    std::vector<ttable> tt;
+    for (auto& b : tables) tt.push_back(tt_from_bytes(b));
+    ttable T = tt_from_bytes(target), M = tt_from_bytes(mask);
+    u64 p1[2], p0[2];
+    if (!lut7_p_masks(tt.data(), T & M, ~T & M, p1, p0)) {
+      return py::make_tuple(false, 0, 0, 0);
+    }
+    u8 ord[7];
+    lut7_ordering(ordering_idx, ord);
+    u8 fo, fm, fi;
+    if (!lut7_solve_ordering(p1, p0, ord, rnd, &fo, &fm, &fi, fm_offset,
+                             fm_count)) {
+      return py::make_tuple(false, 0, 0, 0);
+    }
+    return py::make_tuple(true, static_cast<int>(fo), static_cast<int>(fm),
+                          static_cast<int>(fi));
+  }, py::arg("tables"), py::arg("target"), py::arg("mask"),
+     py::arg("ordering_idx"), py::arg("rnd"), py::arg("fm_offset") = 0,
+     py::arg("fm_count") = 256);
   m.def("splits5", []() {
     py::list out;
     for (auto& sp : SPLITS5) {

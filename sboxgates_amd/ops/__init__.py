@@ -21,6 +21,7 @@ from .._core import (  # noqa: F401
     lut5_solve,
     lut7_ordering,
     lut7_solve,
+    lut7_solve_ordering,
     make_2_input_fun,
     mask_for_inputs,
     n_choose_k,

@@ -2,8 +2,9 @@
 tests: pure Python and numpy, written from the definition of each scan's
 verdict. It takes truth tables as 256-bit integers built from
 `state.gate(i)["table"]` and uses none of the engine's cell algebra (no
-lut5_solve, no lut7_solve, no naive_* helper); the only engine functions it
-calls are gen_lut_ttable / tt_eq_mask, to re-evaluate a reported hit, and
+lut5_solve, no lut7_solve, no lut7_ordering, no naive_* helper); the only
+engine functions it calls are gen_lut_ttable / tt_eq_mask, to re-evaluate a
+reported hit and to build the LUT tables of found7_naive, and
 function_lists, for the list the k=4 result indexes.
 
 Every mask used with it must hold at least one position where the target is
@@ -11,6 +12,7 @@ Every mask used with it must hold at least one position where the target is
 round-trip" special cases, so the oracle needs no knowledge of them.
 """
 
+import collections
 import functools
 import itertools
 import math
@@ -180,6 +182,128 @@ def found5(tabs, target, mask):
     return False
 
 
+# --- the full 7-LUT verdict -------------------------------------------------
+
+# The (outer triple, middle triple, leftover gate) arrangements of seven
+# inputs, as positions into the combination. Swapping the outer and the
+# middle triple gives the same circuit with the first two inputs of fi
+# exchanged, so of each such pair only the one whose outer tuple is the
+# smaller is kept: 35 * 4 / 2 = 70. found7_naive walks all 140.
+ARRANGEMENTS7_ALL = tuple(
+    (outer, middle, (set(range(7)) - set(outer) - set(middle)).pop())
+    for outer in itertools.combinations(range(7), 3)
+    for middle in itertools.combinations(
+        [j for j in range(7) if j not in outer], 3))
+ARRANGEMENTS7 = tuple(a for a in ARRANGEMENTS7_ALL if a[0] < a[1])
+assert len(ARRANGEMENTS7_ALL) == 140 and len(ARRANGEMENTS7) == 70
+
+# _MEET1[a] = the set of bytes fm that share a pattern with the pattern set
+# a (a byte), as a 256-bit row of 32 packed bytes; _MEET0[a] = the set of fm
+# whose complement does.
+_MEET1 = np.packbits((_FO[:, None] & _FO[None, :]) != 0, axis=1,
+                     bitorder="little")
+_MEET0 = np.packbits((_FO[:, None] & ~_FO[None, :] & 255) != 0, axis=1,
+                     bitorder="little")
+
+
+def _bad7(tabs, target, mask, funs):
+    """Per arrangement: (arrangement, bad[fo, fm]), bad being True where some
+    inner cell (o, m, g) holds both target-1 and target-0 content, so that
+    no fi exists. funs restricts fo and fm to a list of function bytes (for
+    the comparison with found7_naive); None is all 256."""
+    pos = positions(mask)
+    tgt = [(target >> p) & 1 for p in pos]
+    bits = [[(t >> p) & 1 for p in pos] for t in tabs]
+    for outer, middle, g in ARRANGEMENTS7:
+        # c[t][u, g]: the middle patterns w seen with outer pattern u,
+        # leftover value g and target bit t, as a byte over w; the first
+        # gate of a triple is the most significant pattern bit.
+        c = np.zeros((2, 8, 2), dtype=np.int64)
+        for i, t in enumerate(tgt):
+            u = sum(bits[j][i] << (2 - n) for n, j in enumerate(outer))
+            w = sum(bits[j][i] << (2 - n) for n, j in enumerate(middle))
+            c[t, u, bits[g][i]] |= 1 << w
+        # sub[f, t, g]: the w-bytes of the u's in the pattern set f (a
+        # byte), OR-ed. The sets whose highest pattern is u are the sets of
+        # lower patterns with u added.
+        sub = np.zeros((256, 2, 2), dtype=np.int64)
+        for u in range(8):
+            sub[1 << u:2 << u] = sub[:1 << u] | c[:, u]
+        # For all 256 fo at once: class o = 1 of fo is the set fo itself,
+        # class 0 the set 255 - fo.
+        wb = np.stack([sub[::-1], sub])
+        w1, w0 = wb[:, :, 1], wb[:, :, 0]
+        # The content of cell (o, m=1, g) is what the class shares with fm;
+        # that of (o, m=0, g), what it shares with ~fm. Rows fo, packed bits
+        # fm, OR-ed over o and g.
+        bad = np.bitwise_or.reduce((_MEET1[w1] & _MEET1[w0])
+                                   | (_MEET0[w1] & _MEET0[w0]), axis=(0, 2))
+        bad = np.unpackbits(bad, axis=1, bitorder="little").astype(bool)
+        if funs is not None:
+            bad = bad[np.ix_(funs, funs)]
+        yield (outer, middle, g), bad
+
+
+def solvable_orderings7(tabs, target, mask, funs=None):
+    """Per solvable arrangement of the seven gates: (outer positions, middle
+    positions, leftover position, number of middle functions fm for which
+    some outer function fo leaves every inner cell uncontradicted)."""
+    out = []
+    for arr, bad in _bad7(tabs, target, mask, funs):
+        n_fm = int((~bad).any(axis=0).sum())
+        if n_fm:
+            out.append(arr + (n_fm,))
+    return out
+
+
+def found7(tabs, target, mask, funs=None):
+    """7-LUT verdict from the definition: some arrangement (outer triple,
+    middle triple, leftover gate g) and some fo, fm, fi among all 256 bytes
+    each give fi(fo(abc), fm(def), g) == target at every masked position.
+    For fixed fo and fm an fi exists iff no inner cell (o, m, g) holds both
+    a target-1 and a target-0 position.
+
+    The engine never emits function byte 00; that does not change the
+    verdict. fo = 00 feeds fi a constant 0 where fo = ff feeds it a constant
+    1, and fi with its first input inverted serves the one as fi serves the
+    other; likewise for fm. fi = 00 makes the circuit constant 0, which
+    cannot match a mask that holds a target-1 position, and every mask used
+    with this oracle does (sparse_mask asserts it)."""
+    return any(not bad.all() for _, bad in _bad7(tabs, target, mask, funs))
+
+
+def found7_naive(tabs, target, mask, funs=range(256)):
+    """The same verdict the slow way, to check found7: all 140 ordered
+    arrangements, fo and fm from funs, the three LUT tables built literally
+    with gen_lut_ttable and fi derived position by position."""
+    pos = positions(mask)
+    tb = [tt_bytes(t) for t in tabs]
+    target_b, mask_b = tt_bytes(target), tt_bytes(mask)
+    lut = {}
+    for triple in itertools.combinations(range(7), 3):
+        for f in funs:
+            lut[triple, f] = gen_lut_ttable(f, *(tb[j] for j in triple))
+    for outer, middle, g in ARRANGEMENTS7_ALL:
+        for fo in funs:
+            t_o = tt_int(lut[outer, fo])
+            for fm in funs:
+                t_m = tt_int(lut[middle, fm])
+                want = {}
+                for p in pos:
+                    pat = (((t_o >> p) & 1) << 2 | ((t_m >> p) & 1) << 1
+                           | (tabs[g] >> p) & 1)
+                    bit = (target >> p) & 1
+                    if want.setdefault(pat, bit) != bit:
+                        break
+                else:
+                    fi = sum(bit << pat for pat, bit in want.items())
+                    t_i = gen_lut_ttable(fi, lut[outer, fo], lut[middle, fm],
+                                         tb[g])
+                    assert tt_eq_mask(target_b, t_i, mask_b)
+                    return True
+    return False
+
+
 # --- re-evaluating a reported hit -------------------------------------------
 
 def hit_ids(k, res):
@@ -272,11 +396,30 @@ def case_setup(case):
     return st, target, mask, math.comb(pool, 3 if k == 4 else k)
 
 
+class Verdict7(collections.namedtuple(
+        "Verdict7", "feasible solvable arrangements")):
+    """k=7 oracle verdicts of one combination: the necessary condition
+    (feasible7), the full verdict (found7) and solvable_orderings7's list,
+    which is empty exactly when the combination is not solvable."""
+
+    @property
+    def tight_fm(self):
+        """The only solvable arrangement admits just an fm and its
+        complement."""
+        return len(self.arrangements) == 1 and self.arrangements[0][3] == 2
+
+
+def verdict7(tabs, target, mask):
+    feasible = feasible7(tabs, target, mask)
+    arrangements = tuple(solvable_orderings7(tabs, target, mask))
+    return Verdict7(feasible, bool(arrangements), arrangements)
+
+
 @functools.lru_cache(maxsize=None)
 def case_reference(case):
     """Per rank: (combination, oracle verdict, CPU found, CPU res). The
     oracle verdict is a bool for k=3/5, None or (function, order) for k=4,
-    and the necessary condition for k=7. Computed once and shared."""
+    and a Verdict7 for k=7. Computed once and shared."""
     k, pool, size = case
     st, target, mask, total = case_setup(case)
     eng = cpu_engine(k)
@@ -295,8 +438,55 @@ def case_reference(case):
         elif k == 5:
             verdict = found5(g, t, m)
         else:
-            verdict = feasible7(g, t, m)
+            verdict = verdict7(g, t, m)
         f_c, r_c, _ = eng.scan_pool(k, st, target, mask, r, r + 1,
                                     seed=SCAN_SEED)
         out.append((comb, verdict, f_c, tuple(r_c)))
     return tuple(out)
+
+
+# --- k=7 windows derived from a per-rank table -------------------------------
+
+WINDOW7_CASE = (7, 11, 24)
+
+
+@functools.lru_cache(maxsize=None)
+def unsolvable_runs7(case):
+    """(begin, end, number of feasible ranks) of every maximal run [begin,
+    end) of ranks the oracle calls unsolvable that holds at least one
+    feasible rank. Rank `end` is solvable, or one past the last rank."""
+    ref = case_reference(case)
+    runs = []
+    begin = 0
+    for r in range(len(ref) + 1):
+        if r < len(ref) and not ref[r][1].solvable:
+            continue
+        feasible = sum(ref[i][1].feasible for i in range(begin, r))
+        if feasible:
+            runs.append((begin, r, feasible))
+        begin = r + 1
+    return tuple(runs)
+
+
+# --- a deep, mostly unsolvable 7-LUT hit list --------------------------------
+
+# Pool 26, rijndael bit 0, sparse_mask(2, 36): ranks [0, DEEP7_FIRST) hold
+# DEEP7_FEASIBLE feasible combinations and no solvable one; rank DEEP7_FIRST,
+# the combination DEEP7_COMB, is solvable. test_oracle.py re-asserts this.
+DEEP7_POOL = 26
+DEEP7_MASK = (2, 36)
+DEEP7_FIRST = 71856
+DEEP7_COMB = [0, 2, 10, 11, 12, 21, 25]
+DEEP7_FEASIBLE = 972
+DEEP7_WINDOWS = ((0, DEEP7_FIRST), (0, DEEP7_FIRST + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def deep7_setup():
+    """(state, target, mask) of the deep instance."""
+    eng = cpu_engine(7)
+    st = eng.initial_state()
+    st.grow_pool_random(DEEP7_POOL, POOL_SEED + DEEP7_POOL)
+    assert st.num_gates == DEEP7_POOL
+    target = eng.target(0)
+    return st, target, sparse_mask(DEEP7_MASK[0], DEEP7_MASK[1], target)

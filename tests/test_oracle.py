@@ -3,12 +3,14 @@ single-rank windows [r, r+1) for every rank of the per-rank cases that
 tests/test_gpu_per_rank.py runs on the GPU. Runs without a GPU, so the
 oracle is kept honest in the suite that runs everywhere."""
 
+import itertools
 import math
 import random
 
 import pytest
 
 import _oracle as orc
+from conftest import rand_sparse_tt, rand_tt
 
 
 def test_unranker_round_trip():
@@ -41,6 +43,75 @@ def test_cells_order_and_verdicts_by_hand():
     assert orc.found4([a, b, c], 0b1000, 0b1111, [0x11, 0xC0]) == (1, 0)
     assert orc.found4([a, b, c], 0b1000, 0b1111, [0x11]) is None
 
+    # k=7 on the seven input variables x0..x6 themselves, full mask: every
+    # cell holds exactly the two positions that differ in x7 alone, on which
+    # both targets below agree, so both are feasible.
+    x = [sum(1 << i for i in range(256) if (i >> j) & 1) for j in range(7)]
+    full = (1 << 256) - 1
+    # AND(x0,x1,x2) ^ OR(x3,x4,x5) ^ x6 is a 7-LUT by construction: fo = 80,
+    # fm = fe, fi = 96. In that arrangement fm must tell pattern 000 from
+    # the seven others, which only OR (fe) and NOR (01) do.
+    t = 0
+    for i in range(256):
+        b = [(i >> j) & 1 for j in range(7)]
+        t |= ((b[0] & b[1] & b[2]) ^ (b[3] | b[4] | b[5]) ^ b[6]) << i
+    assert orc.feasible7(x, t, full) and orc.found7(x, t, full)
+    assert ((0, 1, 2), (3, 4, 5), 6, 2) in orc.solvable_orderings7(x, t, full)
+    assert orc.found7_naive(x, t, full, funs=(0x80, 0xFE, 0x01))
+    # Majority of the seven is feasible but no 7-LUT. Fix the outer triple's
+    # inputs at weight s: what remains is "at least 4 - s of the other four
+    # are 1", a different function of those four for each s = 0..3. fo maps
+    # the outer patterns to one bit, so two of the four weights share a
+    # value of fo, and fi(fo, ., .) is then the same function of the other
+    # four inputs for both. The target is symmetric, so that holds for every
+    # arrangement.
+    maj = sum(1 << i for i in range(256) if bin(i & 127).count("1") >= 4)
+    assert orc.feasible7(x, maj, full)
+    assert not orc.found7(x, maj, full)
+    assert orc.solvable_orderings7(x, maj, full) == []
+
+
+def test_arrangements7_are_the_70_classes():
+    """The oracle's own enumeration: 140 ordered (outer, middle, leftover)
+    arrangements, of which it keeps one per outer/middle swap."""
+    keys = {(frozenset([o, m]), g) for o, m, g in orc.ARRANGEMENTS7_ALL}
+    assert len(keys) == 70
+    assert {(frozenset([o, m]), g) for o, m, g in orc.ARRANGEMENTS7} == keys
+    for o, m, g in orc.ARRANGEMENTS7_ALL:
+        assert sorted(o + m + (g,)) == list(range(7))
+
+
+def test_found7_matches_naive_formulation():
+    """found7 against found7_naive, which builds the three LUT tables and
+    derives fi position by position. The naive form costs about 15 us per
+    (arrangement, fo, fm), so it runs with fo and fm drawn from a random set
+    of 10 function bytes (byte 00 always among them) on masks of up to 24
+    positions, where both verdicts occur, and with all 256 on masks of up
+    to 12 positions that found7 calls solvable."""
+    rng = random.Random(7007)
+    verdicts = []
+    for _ in range(24):
+        tabs = [orc.tt_int(rand_tt(rng)) for _ in range(7)]
+        target = orc.tt_int(rand_tt(rng))
+        mask = orc.tt_int(rand_sparse_tt(rng, rng.choice([8, 12, 16, 24])))
+        funs = [0] + rng.sample(range(1, 256), 9)
+        want = orc.found7_naive(tabs, target, mask, funs)
+        assert orc.found7(tabs, target, mask, funs) == want
+        assert bool(orc.solvable_orderings7(tabs, target, mask, funs)) == want
+        verdicts.append(want)
+    print("restricted function set: %d solvable, %d not"
+          % (verdicts.count(True), verdicts.count(False)))
+    assert verdicts.count(True) >= 5 and verdicts.count(False) >= 5
+    full = 0
+    for _ in range(6):
+        tabs = [orc.tt_int(rand_tt(rng)) for _ in range(7)]
+        target = orc.tt_int(rand_tt(rng))
+        mask = orc.tt_int(rand_sparse_tt(rng, rng.choice([8, 12])))
+        if orc.found7(tabs, target, mask):
+            full += 1
+            assert orc.found7_naive(tabs, target, mask)
+    assert full >= 3
+
 
 @pytest.mark.parametrize("case", orc.PER_RANK_CASES, ids=orc.case_id)
 def test_oracle_matches_cpu_scan_per_rank(case):
@@ -51,7 +122,9 @@ def test_oracle_matches_cpu_scan_per_rank(case):
     hits = 0
     for r, (comb, verdict, f_c, r_c) in enumerate(orc.case_reference(case)):
         if k == 7:
-            assert not f_c or verdict, (r, comb)      # found => feasible
+            assert f_c == verdict.solvable, (r, comb)
+            assert verdict.feasible or not f_c, (r, comb)  # found => feasible
+            assert verdict.feasible or not verdict.solvable, (r, comb)
         elif k == 4:
             assert f_c == (verdict is not None), (r, comb)
             if f_c:
@@ -62,8 +135,87 @@ def test_oracle_matches_cpu_scan_per_rank(case):
             hits += 1
             assert orc.hit_ids(k, r_c) == comb, (r, r_c)
             orc.assert_hit_valid(k, st, r_c, target, mask, threes)
-    # A case must not pass vacuously. For k=3/4/5 the oracle's verdicts equal
-    # the CPU's (asserted above), so this is the share under the oracle.
+    # A case must not pass vacuously. The oracle's verdicts equal the CPU's
+    # (asserted above), so this is the share under the oracle.
     share = hits / total
-    print(f"{orc.case_id(case)}: {hits}/{total} hits ({100 * share:.1f}%)")
+    line = f"{orc.case_id(case)}: {hits}/{total} hits ({100 * share:.1f}%)"
+    if k == 7:
+        line += ("; %d feasible-unsolvable, %d solvable, %d in one arrangement"
+                 ", %d of those with two fm" % k7_counts([case]))
+    print(line)
     assert 0.02 <= share <= 0.98, share
+
+
+K7_CASES = [c for c in orc.PER_RANK_CASES if c[0] == 7]
+
+
+def k7_counts(cases):
+    """Over the ranks of the cases, under the oracle alone: (feasible but
+    unsolvable, solvable, solvable in exactly one arrangement, of those the
+    ones whose arrangement admits only an fm and its complement)."""
+    v = [verdict for case in cases
+         for _, verdict, _, _ in orc.case_reference(case)]
+    return (sum(x.feasible and not x.solvable for x in v),
+            sum(x.solvable for x in v),
+            sum(len(x.arrangements) == 1 for x in v),
+            sum(x.tight_fm for x in v))
+
+
+def test_k7_cases_tell_solvable_from_feasible():
+    """Taken together the k=7 cases must be able to tell a correct solver
+    from one that answers "feasible", from one that loses an arrangement,
+    and from one that loses part of the fm sweep: counted under the oracle
+    alone."""
+    unsolvable, solvable, single, tight = k7_counts(K7_CASES)
+    print("k=7 cases: %d feasible-unsolvable, %d solvable, %d in one "
+          "arrangement, %d of those with two fm"
+          % (unsolvable, solvable, single, tight))
+    assert unsolvable >= 20
+    assert solvable >= 20
+    assert single >= 10
+    assert tight >= 1
+
+
+def test_deep_hit_list_instance():
+    """The facts that the GPU test of the deep, mostly unsolvable hit list
+    (test_gpu_per_rank.py) builds on, from the oracle and the CPU scan."""
+    st, target, mask = orc.deep7_setup()
+    orc.assert_mask_has_target1(target, mask)
+    n = orc.DEEP7_POOL
+    tabs = [orc.tt_int(st.gate(i)["table"]) for i in range(n)]
+    t, m = orc.tt_int(target), orc.tt_int(mask)
+    assert orc.checked_unrank(orc.DEEP7_FIRST, n, 7) == orc.DEEP7_COMB
+    # itertools.combinations walks the combinations in rank order.
+    feasible = [r for r, comb in enumerate(itertools.islice(
+        itertools.combinations(range(n), 7), orc.DEEP7_FIRST))
+        if orc.feasible7([tabs[i] for i in comb], t, m)]
+    assert len(feasible) == orc.DEEP7_FEASIBLE
+    assert orc.found7([tabs[i] for i in orc.DEEP7_COMB], t, m)
+    for r in random.Random(36).sample(feasible, 40):
+        comb = orc.checked_unrank(r, n, 7)
+        assert not orc.found7([tabs[i] for i in comb], t, m), (r, comb)
+    eng = orc.cpu_engine(7)
+    (a0, b0), (a1, b1) = orc.DEEP7_WINDOWS
+    f_c, _, ev = eng.scan_pool(7, st, target, mask, a0, b0, seed=orc.SCAN_SEED)
+    assert not f_c and ev == orc.DEEP7_FIRST
+    f_c, r_c, ev = eng.scan_pool(7, st, target, mask, a1, b1,
+                                 seed=orc.SCAN_SEED)
+    assert f_c and orc.hit_ids(7, r_c) == orc.DEEP7_COMB
+    orc.assert_hit_valid(7, st, r_c, target, mask)
+
+
+def test_window_case_has_unsolvable_runs():
+    """The k=7 window test on the GPU derives its windows from these."""
+    runs = orc.unsolvable_runs7(orc.WINDOW7_CASE)
+    assert len(runs) >= 10
+    ref = orc.case_reference(orc.WINDOW7_CASE)
+    eng = orc.cpu_engine(7)
+    st, target, mask, total = orc.case_setup(orc.WINDOW7_CASE)
+    for begin, end, feasible in runs:
+        assert feasible >= 1
+        assert not any(ref[r][1].solvable for r in range(begin, end))
+        assert end == total or ref[end][1].solvable
+        assert begin == 0 or ref[begin - 1][1].solvable
+        f_c, _, ev = eng.scan_pool(7, st, target, mask, begin, end,
+                                   seed=orc.SCAN_SEED)
+        assert not f_c and ev == end - begin

@@ -458,6 +458,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("permute", &options::permute)
       .def_readwrite("lut_graph", &options::lut_graph)
       .def_readwrite("lut_shared", &options::lut_shared)
+      .def_readwrite("ordered", &options::ordered)
       .def_readwrite("try_nots", &options::try_nots)
       .def_readwrite("verbosity", &options::verbosity)
       .def_readwrite("seeded", &options::seeded)

@@ -5,7 +5,7 @@
 // defaults (gates = AND|OR|XOR, iterations = 1), same conflict rules
 // (-c/-d mutually exclusive, -l/-s mutually exclusive). MI355X additions:
 // --convert-hip, --seed N, --cpu / --gpu, --gpu-pairs, --lut-shared,
-// --output-dir DIR.
+// --ordered, --output-dir DIR.
 //
 // Unlike the reference there is no MPI launcher: --gpus N drives N devices
 // from ONE process (one host thread + one engine per GPU, shared-memory
@@ -78,6 +78,13 @@ void print_help(const char* prog) {
       "                                gates that share an input,\n"
       "                                LUT(LUT(x,y,z),d,s) with s one of x,y,z,\n"
       "                                before the 5-LUT scan.\n"
+      "      --ordered                 Every GPU scan reports the hit of the\n"
+      "                                lowest rank, as the CPU scans do: with\n"
+      "                                --seed the circuit is the same on every\n"
+      "                                run, with and without a GPU. With more\n"
+      "                                than one rank (--gpus, distributed runs)\n"
+      "                                it is reproducible for a fixed number of\n"
+      "                                ranks, not equal to the one-rank result.\n"
       "      --output-dir=DIR          Directory for XML checkpoint files.\n"
       "      --resume-dir=DIR          Write checkpoints to DIR and resume the\n"
       "                                search from the best state file already\n"
@@ -114,7 +121,7 @@ int main(int argc, char** argv) {
 
   enum { OPT_HIP = 1000, OPT_SEED, OPT_CPU, OPT_GPU, OPT_OUTDIR, OPT_HELP,
          OPT_GPUS, OPT_BEAM, OPT_JOBS, OPT_MAXG, OPT_RESUME, OPT_PAIRS,
-         OPT_SHARED };
+         OPT_SHARED, OPT_ORDERED };
   static const struct option long_opts[] = {
       {"available-gates", required_argument, nullptr, 'a'},
       {"convert-c", no_argument, nullptr, 'c'},
@@ -133,6 +140,7 @@ int main(int argc, char** argv) {
       {"gpu", no_argument, nullptr, OPT_GPU},
       {"gpu-pairs", optional_argument, nullptr, OPT_PAIRS},
       {"lut-shared", no_argument, nullptr, OPT_SHARED},
+      {"ordered", no_argument, nullptr, OPT_ORDERED},
       {"output-dir", required_argument, nullptr, OPT_OUTDIR},
       {"resume-dir", required_argument, nullptr, OPT_RESUME},
       {"gpus", required_argument, nullptr, OPT_GPUS},
@@ -199,6 +207,7 @@ int main(int argc, char** argv) {
         }
         break;
       case OPT_SHARED: opt.lut_shared = true; break;
+      case OPT_ORDERED: opt.ordered = true; break;
       case OPT_OUTDIR:
         opt.output_dir = optarg;
         (void)mkdir(optarg, 0755);  // best-effort; open errors surface later

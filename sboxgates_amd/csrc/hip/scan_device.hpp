@@ -1,6 +1,7 @@
 // scan_device.hpp — device-side pieces shared by the scan kernels
 // (scan_kernels.hip) and the persistent k=4 service (scan_service.hip):
-// control block, rank decoders, abort/publish, LDS staging, the
+// control block, rank decoders, abort/publish (and, for ordered scans, the
+// lowest-hit minimum that takes their place), LDS staging, the
 // gate-transposed pool and its per-position cell test, the k=3/k=4 triple
 // walk, the k=2 pair walk and the prefix-batch layer of the k=5/k=7 and
 // shared-input scans.
@@ -42,7 +43,7 @@ struct DevCtl {
   u32 abort;
   u32 lock;
   u32 found;
-  u32 pad;
+  u32 pool_n;  // ordered k=7: the pool size, for k_scan7_assign's ranks
   u16 res[10];
   u16 pad2[3];
   unsigned long long evaluated;
@@ -50,10 +51,16 @@ struct DevCtl {
   unsigned long long hit_count;  // K7 filter
   u32 overflow;                  // K7 filter: hit buffer overflowed
   u32 pad3;
-  // k=2: minimum over the hits of rank << 8 | matcher entry. The host, or
-  // the service leader, sets it to all-ones before every request.
+  // k=2: minimum over the hits of rank << 8 | matcher entry. Ordered scans
+  // (ScanRequest::ordered) of the other kinds: minimum over the hits of
+  // rank << 16 | function << 8 | argument order (k=3 and k=4; k=3 leaves the
+  // low 16 bits zero) or of the plain rank (k=5, k=7, shared-input). The
+  // host, or the service leader, sets it to all-ones before every request.
   unsigned long long best;
 };
+
+// Shift of the rank inside DevCtl::best for ordered k=3 / k=4 scans.
+constexpr int BEST3_SHIFT = 16;
 
 struct Hit7 {
   u64 p1[2];
@@ -192,6 +199,32 @@ __device__ __forceinline__ void dev_publish(DevCtl* ctl, const u16 res[10]) {
     __hip_atomic_store(as_gu32(&ctl->abort), 1u, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// Ordered scans (ScanRequest::ordered): the answer is the hit of the lowest
+// rank, as in walk_pairs. A hit lowers ctl->best with one relaxed agent-scope
+// fetch_min on the global address; nobody takes the lock, publishes a payload
+// or sets the abort flag, and no workgroup waits for another. best is only
+// read to skip work that ranks above it.
+__device__ __forceinline__ void dev_lower_best(DevCtl* ctl, u64 v) {
+  __hip_atomic_fetch_min(as_gu64(&ctl->best), v, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ u64 dev_best(DevCtl* ctl) {
+  return __hip_atomic_load(as_gu64(&ctl->best), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Lexicographic rank of the ascending 7-combination ids of [0, n): the sum
+// decode_prefix_window starts, carried through all seven slots.
+__device__ __forceinline__ i64 dev_rank7(const u16* ids, int n) {
+  i64 r = cf7(n) - cf7(n - ids[0]);
+  r += cf6(n - ids[0] - 1) - cf6(n - ids[1]);
+  r += cf5(n - ids[1] - 1) - cf5(n - ids[2]);
+  r += cf4(n - ids[2] - 1) - cf4(n - ids[3]);
+  r += cf3(n - ids[3] - 1) - cf3(n - ids[4]);
+  r += cf2(n - ids[4] - 1) - cf2(n - ids[5]);
+  return r + (ids[6] - ids[5] - 1);
 }
 
 // What a k=2 request carries besides the pool: the pair matcher and the
@@ -594,9 +627,11 @@ __device__ __forceinline__ void block_add_evaluated(DevCtl* ctl,
 // with stride `stride`, pool staged in LDS by the caller. Every triple
 // whose p-masks are consistent goes to on_feasible(idx, a, b, c, p1, p0);
 // a true return ends this thread's walk. Returns this thread's evaluated
-// count.
+// count. ORD (ordered scan): the poll leaves once the thread's own rank,
+// which only grows, is past the best known (rank << BEST3_SHIFT in
+// ctl->best), instead of reading the abort flag.
 // ---------------------------------------------------------------------------
-template <class OnFeasible>
+template <bool ORD = false, class OnFeasible>
 __device__ __forceinline__ u64 walk_triples(const u64* s_pool, int n,
                                             const ttable& T1, const ttable& T0,
                                             int count_all, DevCtl* ctl,
@@ -605,7 +640,13 @@ __device__ __forceinline__ u64 walk_triples(const u64* s_pool, int n,
   u64 local_eval = 0;
   int tick = 0;
   for (i64 idx = idx0; idx < end; idx += stride) {
-    if (((tick++) & 255) == 0 && !count_all && dev_abort(ctl)) break;
+    if (((tick++) & 255) == 0 && !count_all) {
+      if constexpr (ORD) {
+        if (static_cast<u64>(idx) > (dev_best(ctl) >> BEST3_SHIFT)) break;
+      } else {
+        if (dev_abort(ctl)) break;
+      }
+    }
     int a, b, c;
     dev_decode_triple(idx, n, &a, &b, &c);
 
@@ -716,6 +757,11 @@ __constant__ int c_perm6[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2},
 
 // The k=4 action for walk_triples, matcher staged in LDS by the caller.
 // Used by both the one-shot k_scan4 kernel and the persistent service.
+// ORD (ordered scan): a hit lowers ctl->best with rank << BEST3_SHIFT |
+// function index << 8 | argument order and ends the thread's walk, whose
+// later ranks are all higher; the first order, then the first function, are
+// cpu_scan4's.
+template <bool ORD = false>
 struct Scan4Match {
   const u8* s_bitmap;
   const u8* s_funs;
@@ -723,8 +769,8 @@ struct Scan4Match {
   int count_all;
   DevCtl* ctl;
 
-  __device__ __forceinline__ bool operator()(i64, int a, int b, int c, u32 p1,
-                                             u32 p0) const {
+  __device__ __forceinline__ bool operator()(i64 idx, int a, int b, int c,
+                                             u32 p1, u32 p0) const {
     if (count_all) return false;
     const u8 req1 = static_cast<u8>(p1);
     const u8 care = static_cast<u8>(p1 | p0);
@@ -737,6 +783,12 @@ struct Scan4Match {
       if (!((s_bitmap[bidx >> 3] >> (bidx & 7)) & 1)) continue;
       for (int f = 0; f < s_count; f++) {
         if ((s_funs[f] & cr) == r) {
+          if constexpr (ORD) {
+            dev_lower_best(ctl, static_cast<u64>(idx) << BEST3_SHIFT |
+                                    static_cast<u64>(f) << 8 |
+                                    static_cast<u64>(perm));
+            return true;
+          }
           u16 res[10] = {};
           res[0] = static_cast<u16>(f);
           res[1] = static_cast<u16>(perm);
@@ -749,6 +801,7 @@ struct Scan4Match {
       }
       break;  // bitmap said a function exists; it was found and published
     }
+    if constexpr (ORD) return false;
     return dev_abort(ctl);
   }
 };
@@ -765,14 +818,17 @@ struct Scan4Match {
 // One dequeue per batch: thread 0 takes `units` off ctl->queue and
 // broadcasts the first one through *s_slot. Returns -1 instead when the
 // scan was aborted (or, if watched, the K7 hit buffer overflowed).
-// Contains barriers.
+// Contains barriers. ORD (ordered scan): a known hit takes the abort flag's
+// place. The queue hands out prefixes in increasing order, so every prefix
+// not yet dequeued ranks above any hit already known.
+template <bool ORD = false>
 __device__ __forceinline__ i64 dequeue_batch(DevCtl* ctl, int units,
                                              int count_all, bool watch_overflow,
                                              i64* s_slot) {
   __syncthreads();
   if (threadIdx.x == 0) {
     const bool halt =
-        (!count_all && dev_abort(ctl)) ||
+        (!count_all && (ORD ? dev_best(ctl) != ~0ULL : dev_abort(ctl))) ||
         (watch_overflow &&
          __hip_atomic_load(&ctl->overflow, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT) != 0);

@@ -19,8 +19,18 @@
 //    against per-prefix work. Grids are sized >> 256 CUs.
 //  * Early exit: winner election by atomicCAS on a device-scope lock; an
 //    agent-scope abort flag (sc1, L1-bypassing load) is polled on a coarse
-//    cadence. Any valid winner is acceptable (the reference is equally
-//    nondeterministic across ranks, lut.c:213-218).
+//    cadence. By default any valid winner is acceptable (the reference is
+//    equally nondeterministic across ranks, lut.c:213-218).
+//  * Ordered scans (ScanRequest::ordered): the winner is the hit of the
+//    lowest rank, which is what the CPU scan of the same window returns. A
+//    hit only lowers ctl->best with one fetch_min (dev_lower_best), as the
+//    pair scan does; no lock, no payload, no abort flag, no waiting. best
+//    is read to skip work that ranks above it: the strided walks leave
+//    once past it, the prefix queue stops handing out batches, and a batch
+//    already taken that begins below it runs to its end. The host reads
+//    the rank back and derives the result words with the CPU scan of that
+//    single rank. Every kernel that differs takes the mode as a template
+//    parameter.
 
 #include <algorithm>
 #include <cstdio>
@@ -33,6 +43,7 @@
 #include "sbg/comb.hpp"
 #include "sbg/scan5_geom.hpp"
 #include "scan_device.hpp"
+#include "scan_ordered.hpp"
 #include "scan_service.hpp"
 
 namespace sbg {
@@ -55,7 +66,14 @@ constexpr i64 SLICE_UNIT = 8 * SCAN_BLOCK;
 // K2 — 3-LUT scan. Grid-stride over combination ranks; per-thread decode by
 // binary search on closed-form binomials; cells evaluated directly (the
 // reference's serial rank-0 loop, lut.c:501-523).
+//
+// ORD, here and on the kernels below: the ordered variant (see the Early
+// exit note above), a compile-time parameter so that the default kernels
+// are what they were without it. This file instantiates ORD = false only;
+// scan_ordered.hip includes it with SBG_ORDERED_TU defined and instantiates
+// ORD = true, behind the launchers at the end (why: scan_ordered.hpp).
 // ---------------------------------------------------------------------------
+template <bool ORD>
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan3(ScanArgs args) {
   __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
   load_pool_lds(s_pool, args.pool, args.n);
@@ -65,13 +83,17 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan3(ScanArgs args) {
   const i64 stride = static_cast<i64>(gridDim.x) * blockDim.x;
   const i64 idx0 =
       args.begin + blockIdx.x * static_cast<i64>(blockDim.x) + threadIdx.x;
-  const u64 local_eval = walk_triples(
+  const u64 local_eval = walk_triples<ORD>(
       s_pool, args.n, args.T1, args.T0, args.count_all, ctl, idx0, args.end,
       stride, [&](i64 idx, int a, int b, int c, u32 p1, u32 p0) {
         // Same random word as cpu_scan3 (see scan_rnd in sbg/rng.hpp).
         u8 func = lut3_function_from_p(
             p1, p0, hash_mix64(args.seed ^ static_cast<u64>(idx)));
         if (args.count_all || func == 0) return false;
+        if constexpr (ORD) {
+          dev_lower_best(ctl, static_cast<u64>(idx) << BEST3_SHIFT);
+          return true;
+        }
         u16 res[10] = {};
         res[0] = func;
         res[1] = static_cast<u16>(a);
@@ -85,6 +107,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan3(ScanArgs args) {
 
 // K1c — gate-mode step-4 triple scan, one-shot launch (Scan4Match in
 // scan_device.hpp is the per-triple function search).
+template <bool ORD>
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4(ScanArgs args) {
   __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
   __shared__ alignas(16) u8 s_bitmap[MATCHER_BITMAP_BYTES];
@@ -98,12 +121,13 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4(ScanArgs args) {
   const i64 stride = static_cast<i64>(gridDim.x) * blockDim.x;
   const i64 idx0 =
       args.begin + blockIdx.x * static_cast<i64>(blockDim.x) + threadIdx.x;
-  const u64 local_eval = walk_triples(
+  const u64 local_eval = walk_triples<ORD>(
       s_pool, args.n, args.T1, args.T0, args.count_all, ctl, idx0, args.end,
-      stride, Scan4Match{s_bitmap, s_funs, s_count, args.count_all, ctl});
+      stride, Scan4Match<ORD>{s_bitmap, s_funs, s_count, args.count_all, ctl});
   block_add_evaluated(ctl, local_eval);
 }
 
+#ifndef SBG_ORDERED_TU  // the pair scan has one variant
 // K1p — gate-mode step-3/4a pair scan, one-shot launch: one thread per pair
 // rank, grid-stride, the launch shape of k_scan3. The lowest hit rank lands
 // in ctl->best (walk_pairs in scan_device.hpp); the host derives the result.
@@ -120,6 +144,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan2(ScanArgs args) {
   walk_pairs(s_pool, &s_pair2, args.n, args.T1, args.T0, args.ctl, idx0,
              args.end, stride);
 }
+#endif  // SBG_ORDERED_TU
 
 // ---------------------------------------------------------------------------
 // K3 — 5-LUT scan. Workgroups dequeue triple prefixes; the 8 prefix cells
@@ -134,8 +159,9 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan2(ScanArgs args) {
 // ---------------------------------------------------------------------------
 
 // Survivor handling for k_scan5 (rare path; noinline keeps its registers
-// out of the hot loop's budget). STR: the pool's LDS stride.
-template <int STR>
+// out of the hot loop's budget). STR: the pool's LDS stride. ORD: a hit
+// lowers ctl->best with its rank; the host derives the result words.
+template <int STR, bool ORD>
 __device__ __attribute__((noinline)) void scan5_handle_survivor(
     const ScanArgs& args, DevCtl* ctl, const u64* s_pool, const u16* abc,
     i64 rank, int d, int e) {
@@ -152,6 +178,10 @@ __device__ __attribute__((noinline)) void scan5_handle_survivor(
     return;
   }
   if (args.count_all) return;
+  if constexpr (ORD) {
+    dev_lower_best(ctl, static_cast<u64>(rank));
+    return;
+  }
   const u16 nums[5] = {abc[0], abc[1], abc[2], static_cast<u16>(d),
                        static_cast<u16>(e)};
   const u8* sp = SPLITS5[split];
@@ -166,7 +196,7 @@ __device__ __attribute__((noinline)) void scan5_handle_survivor(
 
 // The same test as the screen's on the remaining live cells of pair (d, e),
 // then the solver. Shared by both walks of k_scan5.
-template <int STR>
+template <int STR, bool ORD>
 __device__ __forceinline__ void scan5_after_screen(
     const ScanArgs& args, DevCtl* ctl, const u64* s_pool,
     const u64 (*H1)[4], const u64 (*H0)[4], const u16* abc, u32 other_live,
@@ -208,7 +238,7 @@ __device__ __forceinline__ void scan5_after_screen(
       return;
     }
   }
-  scan5_handle_survivor<STR>(args, ctl, s_pool, abc, rank, d, e);
+  scan5_handle_survivor<STR, ORD>(args, ctl, s_pool, abc, rank, d, e);
 }
 
 // LDS pointers, for k_scan5's arrays as arguments of its wide walk (a plain
@@ -226,7 +256,7 @@ typedef __attribute__((address_space(3))) const u8 lds_cu8;
 // inlined: the kernel's other walk needs most of the register file, and
 // inside the kernel this loop's invariants were spilled and reloaded from
 // scratch in every task; as a function it gets registers of its own.
-template <int STR>
+template <int STR, bool ORD>
 __device__ __attribute__((noinline)) u64 scan5_wide_walk(
     const ScanArgs& args, DevCtl* ctl, int pad, int total_tasks,
     lds_cu64* l_pool, lds_cu32* l_G, lds_cu32* l_tpre, lds_cu32* l_rec,
@@ -253,7 +283,9 @@ __device__ __attribute__((noinline)) u64 scan5_wide_walk(
       since_poll += GB;
       if (since_poll >= 64) {
         since_poll = 0;
-        if (dev_abort(ctl)) break;
+        // An ordered scan runs a batch it has begun to its end: the batch
+        // lies below the best hit known when it was taken.
+        if (!ORD && dev_abort(ctl)) break;
       }
     }
     // Task counts are padded to the wave size, so a wave holds one
@@ -315,9 +347,9 @@ __device__ __attribute__((noinline)) u64 scan5_wide_walk(
     while (pend != 0) {
       const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
       pend &= pend - 1;
-      scan5_after_screen<STR>(args, ctl, s_pool, s_H1[t], s_H0[t], s_abc[t],
-                              live & ~(1u << u0), s_base[t] + q0 + i, d,
-                              e0 + i);
+      scan5_after_screen<STR, ORD>(args, ctl, s_pool, s_H1[t], s_H0[t],
+                                   s_abc[t], live & ~(1u << u0),
+                                   s_base[t] + q0 + i, d, e0 + i);
     }
   }
   return local_eval;
@@ -329,7 +361,7 @@ __device__ __attribute__((noinline)) u64 scan5_wide_walk(
 // batch with such a row through the wide walk. The host picks the variant
 // by pool size, so pools without long rows run the 48 B-stride kernel
 // with no transposed pool to build.
-template <bool WIDE>
+template <bool WIDE, bool ORD>
 __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   // Triple batching: one dequeue + one cooperative prefix-cell build + one
   // barrier per TB triples (measured at TB=1: 48% of wave time parked on
@@ -385,7 +417,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
 
   for (;;) {
     const i64 batch_base =
-        dequeue_batch(ctl, TB, args.count_all, false, &s_batch);
+        dequeue_batch<ORD>(ctl, TB, args.count_all, false, &s_batch);
     if (batch_base < 0) break;
 
     // Threads 0..TB-1 decode one triple each and compute its pair window.
@@ -408,6 +440,11 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       // is past the range end (or past the triple space), every later
       // batch is too.
       s_stop = (batch_base >= total3 || s_base[0] >= args.end) ? 1 : 0;
+      // Ordered: a batch that begins above the best hit known holds nothing
+      // that can lower it, and neither does any later batch.
+      if constexpr (ORD) {
+        if (!s_stop && static_cast<u64>(s_base[0]) > dev_best(ctl)) s_stop = 1;
+      }
       // Row-segment tasks. A task is (triple, row d2, segment): the pairs
       // (d2, e2) with gap e2 - d2 - 1 in [s0, s0 + L). Segment s0 exists for
       // the rows d2 < m - 1 - s0, so a triple has sum_s (m - 1 - s * L)
@@ -503,7 +540,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
     // Wide walk (scan5_wide_walk).
     if constexpr (WIDE) {
       if (s_wide) {
-        local_eval += scan5_wide_walk<STR>(
+        local_eval += scan5_wide_walk<STR, ORD>(
             args, ctl, pad, total_tasks, (lds_cu64*)s_pool, (lds_cu32*)s_G,
             (lds_cu32*)s_tpre, (lds_cu32*)s_rec, (lds_cu8*)s_pos,
             (lds_cu64*)s_H1, (lds_cu64*)s_H0, (lds_cu16*)s_abc,
@@ -523,7 +560,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
         since_poll += L;
         if (since_poll >= 64) {
           since_poll = 0;
-          if (dev_abort(ctl)) break;
+          if (!ORD && dev_abort(ctl)) break;  // ordered: see the wide walk
         }
       }
       int t = 0;
@@ -625,9 +662,9 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
       while (pend != 0) {
         const int i = __ffs(pend) - 1;
         pend &= pend - 1;
-        scan5_after_screen<STR>(args, ctl, s_pool, s_H1[t], s_H0[t], s_abc[t],
-                                live & ~(1u << u0), s_base[t] + q_seg + i, d,
-                                e_first + i);
+        scan5_after_screen<STR, ORD>(args, ctl, s_pool, s_H1[t], s_H0[t],
+                                     s_abc[t], live & ~(1u << u0),
+                                     s_base[t] + q_seg + i, d, e_first + i);
       }
     }
   }
@@ -647,6 +684,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
 
 // Survivor handling for k_scan4s (noinline, as scan5_handle_survivor): exact
 // 16-cell p-masks, then the solver.
+template <bool ORD>
 __device__ __attribute__((noinline)) void scan4s_handle_survivor(
     const ScanArgs& args, DevCtl* ctl, const u64* s_pool, const u16* abc,
     i64 rank, int d) {
@@ -663,6 +701,10 @@ __device__ __attribute__((noinline)) void scan4s_handle_survivor(
     return;
   }
   if (args.count_all) return;
+  if constexpr (ORD) {
+    dev_lower_best(ctl, static_cast<u64>(rank));
+    return;
+  }
   u8 pos[5];
   lut4s_shape_gates(shape, pos);
   u16 res[10] = {};
@@ -672,6 +714,7 @@ __device__ __attribute__((noinline)) void scan4s_handle_survivor(
   dev_publish(ctl, res);
 }
 
+template <bool ORD>
 __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan4s(ScanArgs args) {
   __shared__ alignas(16) u64 s_pool[MAX_GATES * PSTR];
   __shared__ alignas(16) u64 s_H1[SB][8][4];
@@ -694,7 +737,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan4s(ScanArgs args) {
 
   for (;;) {
     const i64 batch_base =
-        dequeue_batch(ctl, SB, args.count_all, false, &s_batch);
+        dequeue_batch<ORD>(ctl, SB, args.count_all, false, &s_batch);
     if (batch_base < 0) break;
 
     if (threadIdx.x < SB) {
@@ -714,6 +757,9 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan4s(ScanArgs args) {
       // index, so once the batch's first triple is past the range end (or
       // past the triple space), every later batch is too.
       s_stop = (batch_base >= total3 || s_base[0] >= args.end) ? 1 : 0;
+      if constexpr (ORD) {  // as in k_scan5
+        if (!s_stop && static_cast<u64>(s_base[0]) > dev_best(ctl)) s_stop = 1;
+      }
       for (int t = 0; t < SB; t++) s_prefix[t + 1] += s_prefix[t];
     }
     __syncthreads();
@@ -729,7 +775,10 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan4s(ScanArgs args) {
 
     int it = 0;
     for (int idx = threadIdx.x; idx < total_cands; idx += blockDim.x) {
-      if (((it++) & 15) == 0 && !args.count_all && dev_abort(ctl)) break;
+      // Ordered: a batch that was begun runs to its end, as in k_scan5.
+      if (!ORD && ((it++) & 15) == 0 && !args.count_all && dev_abort(ctl)) {
+        break;
+      }
       // The prefix of candidate idx: the last t with s_prefix[t] <= idx.
       int t = 0;
 #pragma unroll
@@ -762,13 +811,15 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan4s(ScanArgs args) {
         if ((a1 != 0 && a0 != 0) || (n1 != 0 && n0 != 0)) ok = false;
       }
       if (!ok) continue;
-      scan4s_handle_survivor(args, ctl, s_pool, s_abc[t], s_base[t] + q, d);
+      scan4s_handle_survivor<ORD>(args, ctl, s_pool, s_abc[t], s_base[t] + q,
+                                  d);
     }
   }
 
   block_add_evaluated(ctl, local_eval);
 }
 
+#ifndef SBG_ORDERED_TU  // the filter has one variant: no hit ever aborts it
 // ---------------------------------------------------------------------------
 // K4a — 7-LUT feasibility filter. Workgroups dequeue quadruple prefixes;
 // 16 prefix cells in LDS; threads screen (e, f, g) triples; survivors'
@@ -953,12 +1004,21 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan7_filter(ScanArgs args) {
 
   block_add_evaluated(ctl, local_eval);
 }
+#endif  // SBG_ORDERED_TU
 
 // ---------------------------------------------------------------------------
 // K4b — 7-LUT function assignment over filtered hits: one thread per
 // (hit, ordering); each runs the middle-function sweep + outer 2-coloring
 // (replacing the reference's 70 x 256 x 256 brute force, lut.c:416-484).
+//
+// ORD: the filter appends its hits in no particular order, so an item that
+// solves lowers ctl->best with the rank of its hit's combination (computed
+// here from the hit's gate ids, dev_rank7; Hit7 keeps its size) and the
+// thread goes on: a later item of its own may belong to a lower rank. Items
+// of hits that rank above the best known are skipped. The pool size that
+// the rank needs comes in ctl->pool_n, so both variants keep one signature.
 // ---------------------------------------------------------------------------
+template <bool ORD>
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan7_assign(
     const Hit7* hits, unsigned long long nhits, DevCtl* ctl, u64 seed) {
   // One thread per (hit, ordering, fm-octant): the 256-middle-function
@@ -971,10 +1031,18 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan7_assign(
   int tick = 0;
   for (u64 item = blockIdx.x * static_cast<u64>(blockDim.x) + threadIdx.x;
        item < nitems; item += stride) {
-    if (((tick++) & 3) == 0 && dev_abort(ctl)) return;
+    if constexpr (!ORD) {
+      if (((tick++) & 3) == 0 && dev_abort(ctl)) return;
+    }
     const u64 base_item = item / FM_SPLIT;
     const int oct = static_cast<int>(item % FM_SPLIT);
     const Hit7& h = hits[base_item / LUT7_NUM_ORDERINGS];
+    u64 rank = 0;
+    if constexpr (ORD) {
+      rank = static_cast<u64>(
+          dev_rank7(h.nums, static_cast<int>(ctl->pool_n)));
+      if (rank >= dev_best(ctl)) continue;
+    }
     int oidx = static_cast<int>(base_item % LUT7_NUM_ORDERINGS);
     u8 ord[7];
     lut7_ordering(oidx, ord);
@@ -983,6 +1051,10 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan7_assign(
     // shuffled middle-function order disjointly.
     if (lut7_solve_ordering(h.p1, h.p0, ord, scan_rnd(seed, base_item), &fo,
                             &fm, &fi, oct * FM_SLICE, FM_SLICE)) {
+      if constexpr (ORD) {
+        dev_lower_best(ctl, rank);
+        continue;
+      }
       u16 res[10];
       res[0] = fo;
       res[1] = fm;
@@ -996,6 +1068,33 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan7_assign(
 
 }  // namespace
 
+#ifdef SBG_ORDERED_TU
+// ---------------------------------------------------------------------------
+// Launchers of the ordered variants (scan_ordered.hpp).
+// ---------------------------------------------------------------------------
+
+void launch_ordered_scan(OrderedScan which, int grid, hipStream_t stream,
+                         const void* scan_args) {
+  const ScanArgs& args = *static_cast<const ScanArgs*>(scan_args);
+  void (*kernel)(ScanArgs) = nullptr;
+  switch (which) {
+    case ORDERED_SCAN3: kernel = k_scan3<true>; break;
+    case ORDERED_SCAN4: kernel = k_scan4<true>; break;
+    case ORDERED_SCAN5_ROWS: kernel = k_scan5<false, true>; break;
+    case ORDERED_SCAN5_WIDE: kernel = k_scan5<true, true>; break;
+    case ORDERED_SCAN4S: kernel = k_scan4s<true>; break;
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SCAN_BLOCK), 0, stream, args);
+}
+
+void launch_ordered_assign7(int grid, hipStream_t stream, const void* hits,
+                            unsigned long long nhits, void* ctl, u64 seed) {
+  hipLaunchKernelGGL(k_scan7_assign<true>, dim3(grid), dim3(SCAN_BLOCK), 0,
+                     stream, static_cast<const Hit7*>(hits), nhits,
+                     static_cast<DevCtl*>(ctl), seed);
+}
+
+#else  // !SBG_ORDERED_TU
 // ---------------------------------------------------------------------------
 // GpuEngine host wrapper.
 // ---------------------------------------------------------------------------
@@ -1046,10 +1145,18 @@ struct GpuEngine::Impl {
   // One launch round trip: upload h_ctl, launch, download h_ctl, wait.
   template <class... Params, class... Args>
   void run(void (*kernel)(Params...), int grid, Args&&... args) {
+    run_with([&] {
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(SCAN_BLOCK), 0, stream,
+                         static_cast<Params>(args)...);
+    });
+  }
+
+  // The same round trip around any launch on `stream`.
+  template <class Launch>
+  void run_with(Launch launch) {
     SBG_HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(DevCtl),
                                  hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(SCAN_BLOCK), 0, stream,
-                       static_cast<Params>(args)...);
+    launch();
     SBG_HIP_CHECK(hipGetLastError());
     SBG_HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(DevCtl),
                                  hipMemcpyDeviceToHost, stream));
@@ -1066,6 +1173,31 @@ static void prefix_rank_span(int n, int k, int np, i64 begin, i64 end,
   *first = combination_rank(comb, np, n);
   nth_combination(end - 1, n, k, 0, comb);
   *last = combination_rank(comb, np, n);
+}
+
+// Ordered scans: the kernels report only the rank of the lowest hit. Its
+// result words are those of the CPU scan of the single-rank window
+// [rank, rank + 1), so they are the CPU's by construction. A miss there
+// means kernel and CPU disagree about a candidate: that is an error, never
+// a miss of the scan.
+static ScanResult ordered_result(int k, const ScanRequest& rq, u64 rank,
+                                 u64 evaluated) {
+  const i64 r = static_cast<i64>(rank);
+  ScanResult out;
+  switch (k) {
+    case 3: out = cpu_scan3(rq, r, r + 1); break;
+    case 4: out = cpu_scan4(rq, r, r + 1); break;
+    case 5: out = cpu_scan5(rq, r, r + 1); break;
+    case 7: out = cpu_scan7(rq, r, r + 1); break;
+    default: out = cpu_scan4s(rq, r, r + 1); break;
+  }
+  if (!out.found) {
+    throw std::runtime_error(
+        "ordered scan k=" + std::to_string(k) + ": rank " +
+        std::to_string(rank) + " hits on the GPU and misses on the CPU");
+  }
+  out.evaluated = evaluated;
+  return out;
 }
 
 bool gpu_available() { return gpu_count() > 0; }
@@ -1152,6 +1284,8 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
 
   Impl* im = impl_;
   SBG_HIP_CHECK(hipSetDevice(im->device));
+  // count_all ignores the option; the pair scan is ordered as it is.
+  const bool ordered = rq.ordered && !rq.count_all && k != 2;
 
   // Service only for small/medium ranges: its 64-WG grid is sized for the
   // request/response round trip, not for multi-million-candidate scans —
@@ -1181,6 +1315,18 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   SBG_HIP_CHECK(hipMemcpyAsync(im->d_pool, im->h_pool, sizeof(ttable) * rq.n,
                                hipMemcpyHostToDevice, im->stream));
   std::memset(im->h_ctl, 0, sizeof(DevCtl));
+  if (ordered) im->h_ctl->best = ~0ULL;
+
+  // One-shot launch of a kernel in the mode of this scan.
+  const auto launch = [&](void (*kernel)(ScanArgs), OrderedScan ord, int grid,
+                          const ScanArgs& a) {
+    if (ordered) {
+      im->run_with(
+          [&] { launch_ordered_scan(ord, grid, im->stream, &a); });
+    } else {
+      im->run(kernel, grid, a);
+    }
+  };
 
   ScanArgs args;
   args.pool = im->d_pool;
@@ -1222,7 +1368,11 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
     i64 range = end - begin;
     int grid = static_cast<int>(std::min<i64>((range + SCAN_BLOCK - 1) / SCAN_BLOCK,
                                               4096));
-    im->run(k == 3 ? k_scan3 : k_scan4, grid, args);
+    if (k == 3) {
+      launch(k_scan3<false>, ORDERED_SCAN3, grid, args);
+    } else {
+      launch(k_scan4<false>, ORDERED_SCAN4, grid, args);
+    }
   } else if (k == 5) {
     // Seed the triple queue at the triple containing `begin`.
     i64 t_begin, t_last;
@@ -1236,9 +1386,9 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
     // Pools without a row longer than the crossover never take the wide
     // walk: they get the variant that has no transposed pool to build.
     if (rq.n - 3 > SCAN5_WIDE_MIN_ROW) {
-      im->run(k_scan5<true>, grid, args);
+      launch(k_scan5<true, false>, ORDERED_SCAN5_WIDE, grid, args);
     } else {
-      im->run(k_scan5<false>, grid, args);
+      launch(k_scan5<false, false>, ORDERED_SCAN5_ROWS, grid, args);
     }
   } else if (k == SCAN_SHARED) {
     // Seed the triple queue at the triple containing `begin`; grid sized to
@@ -1249,7 +1399,7 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
     const i64 tcount = t_last - t_begin + 1;
     const int grid =
         static_cast<int>(std::min<i64>((tcount + SB - 1) / SB + 1, 2048));
-    im->run(k_scan4s, grid, args);
+    launch(k_scan4s<false>, ORDERED_SCAN4S, grid, args);
   } else if (k == 7) {
     if (im->d_hits == nullptr) {
       SBG_HIP_CHECK(hipMalloc(&im->d_hits, sizeof(Hit7) * im->hit_cap));
@@ -1262,6 +1412,10 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
       i64 hi = end;
       for (;;) {
         std::memset(im->h_ctl, 0, sizeof(DevCtl));
+        if (ordered) {
+          im->h_ctl->best = ~0ULL;
+          im->h_ctl->pool_n = static_cast<u32>(rq.n);
+        }
         i64 q_begin, q_last;
         prefix_rank_span(rq.n, 7, 4, lo, hi, &q_begin, &q_last);
         i64 qcount = q_last - q_begin + 1;
@@ -1298,7 +1452,20 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
             std::min<u64>((items + SCAN_BLOCK - 1) / SCAN_BLOCK, 4096));
         // h_ctl still holds the filter's final state, which the upload
         // puts back unchanged.
-        im->run(k_scan7_assign, grid, im->d_hits, nhits, im->d_ctl, rq.seed);
+        if (ordered) {
+          im->run_with([&] {
+            launch_ordered_assign7(grid, im->stream, im->d_hits, nhits,
+                                   im->d_ctl, rq.seed);
+          });
+        } else {
+          im->run(k_scan7_assign<false>, grid, im->d_hits, nhits, im->d_ctl,
+                  rq.seed);
+        }
+        // Ordered: the sub-ranges come in increasing order, so the first one
+        // with a hit holds the scan's lowest.
+        if (ordered && im->h_ctl->best != ~0ULL) {
+          return ordered_result(7, rq, im->h_ctl->best, out.evaluated);
+        }
         if (im->h_ctl->found != 0) {
           out.found = true;
           std::memcpy(out.res, im->h_ctl->res, sizeof(out.res));
@@ -1313,11 +1480,18 @@ ScanResult GpuEngine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
   }
 
   out.evaluated = im->h_ctl->evaluated;
+  if (ordered && im->h_ctl->best != ~0ULL) {
+    const u64 best = im->h_ctl->best;
+    return ordered_result(k, rq, k <= 4 ? best >> BEST3_SHIFT : best,
+                          out.evaluated);
+  }
   if (im->h_ctl->found != 0) {
     out.found = true;
     std::memcpy(out.res, im->h_ctl->res, sizeof(out.res));
   }
   return out;
 }
+
+#endif  // SBG_ORDERED_TU
 
 }  // namespace sbg

@@ -53,7 +53,8 @@ enum {
   HDR_BEGIN = 2,
   HDR_END = 3,
   HDR_OP = 4,         // scan kind: 4 (triples) or 2 (pairs)
-                      // 5..7 reserved
+  HDR_ORDERED = 5,    // k=4: nonzero for an ordered scan (lowest hit rank)
+                      // 6..7 reserved
   HDR_T1 = 8,         // 8..11
   HDR_T0 = 12,        // 12..15
   HDR_WORDS = 16,
@@ -265,6 +266,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
       T0.w[w] = s_hdr[HDR_T0 + w];
     }
     const bool pairs = s_hdr[HDR_OP] == 2;
+    const bool ordered = !pairs && s_hdr[HDR_ORDERED] != 0;
     load_pool_lds(s_pool, dev->pool, n);
     if (pairs) {
       copy_pair2_stage(s_pair2, &dev->pair2);
@@ -283,10 +285,15 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
       // Every wave's fetch_min has landed before the barriers below let
       // thread 0 take its ticket.
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      local_eval = walk_triples(
+    } else if (ordered) {
+      local_eval = walk_triples<true>(
           s_pool, n, T1, T0, count_all, &dev->ctl, idx0, end, stride,
-          Scan4Match{s_bitmap, s_funs, s_count, count_all, &dev->ctl});
+          Scan4Match<true>{s_bitmap, s_funs, s_count, count_all, &dev->ctl});
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // as for pairs
+    } else {
+      local_eval = walk_triples<false>(
+          s_pool, n, T1, T0, count_all, &dev->ctl, idx0, end, stride,
+          Scan4Match<false>{s_bitmap, s_funs, s_count, count_all, &dev->ctl});
     }
 
     // ---- completion: last workgroup publishes the response ----
@@ -332,6 +339,21 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan4_service(SvcMailbox* mb,
             rw[0] = (best & 0x7F) | (swapped ? 1ULL << 16 : 0) |
                     (swapped ? y : x) << 32 | (swapped ? x : y) << 48;
             ev = static_cast<unsigned long long>(rank - begin + 1);
+          }
+        } else if (ordered) {
+          // Likewise (layout: cpu_scan4). The walk only visits ranks of the
+          // window, so a hit lies inside it.
+          const unsigned long long best = __hip_atomic_load(
+              as_gu64(&dev->ctl.best), __ATOMIC_RELAXED,
+              __HIP_MEMORY_SCOPE_AGENT);
+          found = best != ~0ULL;
+          if (found != 0) {
+            int a, b, c;
+            dev_decode_triple(static_cast<i64>(best >> BEST3_SHIFT), n, &a, &b,
+                              &c);
+            rw[0] = ((best >> 8) & 0xFF) | (best & 0xFF) << 16 |
+                    static_cast<u64>(a) << 32 | static_cast<u64>(b) << 48;
+            rw[1] = static_cast<u64>(c);
           }
         } else if (found != 0) {
           for (int i = 0; i < 10; i++) {
@@ -594,6 +616,7 @@ ScanResult ScanService::request(int op, const ScanRequest& rq, i64 begin,
   mb_->hdr[HDR_BEGIN] = static_cast<u64>(begin);
   mb_->hdr[HDR_END] = static_cast<u64>(end);
   mb_->hdr[HDR_OP] = static_cast<u64>(op);
+  mb_->hdr[HDR_ORDERED] = op == 4 && rq.ordered && !rq.count_all ? 1 : 0;
   for (int w = 0; w < 4; w++) {
     mb_->hdr[HDR_T1 + w] = T1.w[w];
     mb_->hdr[HDR_T0 + w] = T0.w[w];

@@ -349,8 +349,12 @@ ScanResult Engine::scan_pairs(const ScanRequest& rq, i64 begin, i64 end) {
   return cpu_scan2(rq, begin, end);
 }
 
-ScanResult Engine::scan(int k, const ScanRequest& rq, i64 begin, i64 end) {
-  if (k == 2) return scan_pairs(rq, begin, end);
+ScanResult Engine::scan(int k, const ScanRequest& rq_in, i64 begin, i64 end) {
+  if (k == 2) return scan_pairs(rq_in, begin, end);
+  // options::ordered: the GPU scan answers as the CPU scan would, so which
+  // side runs a scan below changes the time it takes and nothing else.
+  ScanRequest rq = rq_in;
+  rq.ordered = rq.ordered || opt_.ordered;
   // Per-k GPU cutover: per-combination cost grows steeply with k (a 7-LUT
   // feasibility check walks 128 cells vs 32 for 5-LUT and 8 for 3-LUT), so
   // the range size where the GPU (incl. ~20-40us launch+upload overhead)

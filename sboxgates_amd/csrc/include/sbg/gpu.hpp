@@ -33,9 +33,14 @@ class GpuEngine {
   // Scans combinations [begin, end) of C(rq.n, k), k in {2,3,4,5,7} (k=4
   // ranks triples), or of C(rq.n, 4) for k = SCAN_SHARED (one-shot kernel
   // k_scan4s, never the scan service). Blocking; early-exits via an in-kernel abort flag
-  // unless rq.count_all. k=2 is the pair scan: it needs rq.matcher2,
-  // reports the hit of the lowest rank (see cpu_scan2) and, like k=4, goes
-  // through the scan service when that is active.
+  // unless rq.count_all, and then reports whichever hit won the election.
+  // With rq.ordered it reports the hit of the lowest rank instead: found and
+  // res[10] are exactly those of the matching cpu_scanK on the same window
+  // (evaluated is then only known to lie in [1, window size]); a candidate
+  // that hits on the GPU and misses on the CPU throws. k=2 is the pair
+  // scan: it needs rq.matcher2, always reports the hit of the lowest rank
+  // (see cpu_scan2) and, like k=4, goes through the scan service when that
+  // is active.
   ScanResult scan(int k, const ScanRequest& rq, i64 begin, i64 end);
 
   // True when k=4 scans go through the persistent scan-service kernel

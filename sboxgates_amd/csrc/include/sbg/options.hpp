@@ -71,6 +71,13 @@ struct options {
   bool lut_shared = false;  // --lut-shared: LUT mode also tries two LUTs that
                             // share an input, LUT(LUT(x,y,z), d, s) with s
                             // one of x, y, z, before the 5-LUT scan
+  bool ordered = false;     // --ordered: every GPU scan reports the hit of the
+                            // lowest rank, i.e. what the CPU scan of the same
+                            // window reports, so a seeded search finds the
+                            // same circuit with and without a GPU. With more
+                            // than one rank the result is reproducible for a
+                            // fixed world and chunk size, not equal to the
+                            // single-rank one. No effect without a GPU.
   int gpu_device = -1;      // HIP device index; -1 = current device
   int num_gpus = 1;         // CLI --gpus: in-process devices (threads)
   int beam = 20;            // --beam: tied-state beam width (<= 20; the

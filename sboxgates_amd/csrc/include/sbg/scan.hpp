@@ -11,8 +11,12 @@
 //   7-LUT: res[0]=fo, res[1]=fm, res[2]=fi, res[3..9]=gate ids
 // The shared-input two-LUT scan (SCAN_SHARED) reports in the 5-LUT layout,
 // with res[6] equal to one of res[2..4].
-// The pair scan (k=2, gate-mode steps 3 and 4a) is the exception: it
-// reports the hit of the lowest rank, see cpu_scan2.
+// "First" is exact on the CPU: the scans walk in rank order, and the random
+// word of a candidate is keyed on (seed, rank). The GPU kernels by default
+// report whichever hit wins their election; a request with `ordered` set
+// makes them report the hit of the lowest rank, with the CPU's result words.
+// The pair scan (k=2, gate-mode steps 3 and 4a) always reports the hit of
+// the lowest rank, on both sides, see cpu_scan2.
 #pragma once
 
 #include <vector>
@@ -69,6 +73,11 @@ struct ScanRequest {
   // k=2 scans only: visit position j holds gate order[j], a permutation of
   // the pool ids; null is the identity.
   const gatenum* order = nullptr;
+  // GPU scans only (options::ordered): report the hit of the lowest rank in
+  // the window, which is what the CPU scan of that window returns, res[10]
+  // word for word, instead of whichever hit wins the election. The CPU
+  // scans walk in rank order and need no flag; count_all ignores it.
+  bool ordered = false;
 };
 
 // Exclusion mask of a request from the multiplexer input bits already used

@@ -121,6 +121,36 @@ int main() {
     CHECK(circuit_bit_ok(st, sbox, 6, 0));
   }
 
+  // options::ordered on an engine without a GPU: accepted, and the seeded
+  // LUT-mode search finds the circuit it finds without the option (the CPU
+  // scans are ordered already; Engine::scan only marks the request).
+  {
+    std::string xml[2];
+    for (int ordered = 0; ordered < 2; ordered++) {
+      options opt;
+      opt.set_avail_gates(DEFAULT_GATE_BITFIELD);
+      opt.seeded = true;
+      opt.seed = 3;
+      opt.gpu = GPU_OFF;
+      opt.lut_graph = true;
+      opt.ordered = ordered != 0;
+      opt.save_states = false;
+      opt.verbosity = -1;
+      opt.derive_function_lists();
+      Engine eng(opt);
+      eng.set_sbox(sbox, 6);
+      state st;
+      eng.initial_state(st);
+      i8 bits[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+      gatenum out = eng.create_circuit(&st, eng.target(0), tt_mask_for_inputs(6), bits);
+      CHECK(out != NO_GATE);
+      st.outputs[0] = out;
+      CHECK(circuit_bit_ok(st, sbox, 6, 0));
+      xml[ordered] = state_to_xml(st);
+    }
+    CHECK(xml[0] == xml[1]);
+  }
+
   // Scans with planted solutions over a random pool.
   {
     state st;

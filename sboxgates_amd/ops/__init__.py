@@ -39,7 +39,7 @@ def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
                 iterations=1, metric="gates", try_nots=False,
                 save_states=False, output_dir="", verbosity=-1,
                 gate_bitfield=None, ctx=None, jobs=1, gpu_pairs="off",
-                lut_shared=False):
+                lut_shared=False, ordered=False):
     """Builds an Engine with the given search options.
 
     gpu_pairs routes the pair sweeps of gate-mode steps 3 and 4a on an engine
@@ -51,6 +51,18 @@ def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
     3-LUT and the 5-LUT scan of every node: two LUTs over four gates,
     LUT(LUT(x, y, z), d, s) with s one of x, y, z. Off, the search is
     exactly what it was without the option.
+
+    ordered makes every scan that runs on the GPU report the hit of the
+    lowest rank in its window, which is exactly what the CPU scan of that
+    window reports (found and res[10]; evaluated is only known to lie in
+    [1, window size] on a hit). A seeded search then finds the same circuit
+    on every run, under gpu="off", "auto" and "force" alike, and scan_pool /
+    scan_shared on the engine inherit the contract. count_all scans ignore
+    it; an engine without a GPU accepts it and is unchanged, its scans being
+    ordered already. With a ctx of more than one rank the search is
+    reproducible for a fixed world and chunk size, but not equal to the
+    single-rank search. Off (the default), the GPU scans report whichever
+    hit wins their election.
     """
     if lut_shared and not lut_graph:
         raise ValueError("lut_shared needs lut_graph")
@@ -62,6 +74,7 @@ def make_engine(lut_graph=False, seed=None, gpu="auto", oneoutput=-1,
     o.gpu = gpu
     o.gpu_pairs = gpu_pairs
     o.lut_shared = lut_shared
+    o.ordered = ordered
     o.oneoutput = oneoutput
     o.iterations = iterations
     o.jobs = jobs

@@ -1,10 +1,10 @@
-// scan_device.hpp — device-side pieces shared by the scan kernels
-// (scan_kernels.hip) and the persistent k=4 service (scan_service.hip):
-// control block, rank decoders, abort/publish (and, for ordered scans, the
-// lowest-hit minimum that takes their place), LDS staging, the
-// gate-transposed pool and its per-position cell test, the k=3/k=4 triple
-// walk, the k=2 pair walk and the prefix-batch layer of the k=5/k=7 and
-// shared-input scans.
+// scan_device.hpp — device-side pieces shared by the persistent k=4 / k=2
+// service (scan_service.hip) and the one-shot kernel families (scan_*.hpp),
+// or by at least two of those families: rank decoders, abort/publish (and,
+// for ordered scans, the lowest-hit minimum that takes their place), LDS
+// staging, the k=3/k=4 triple walk, the k=2 pair walk and the prefix-batch
+// layer of the k=5/k=7 and shared-input scans. The plain types they work on
+// (control block, kernel arguments) are in scan_types.hpp.
 //
 // Everything here is __device__ __forceinline__ or has internal linkage, so
 // each .hip file is a self-contained translation unit (no relocatable
@@ -15,59 +15,13 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <stdexcept>
-#include <string>
-
 #include "sbg/gpu.hpp"
 #include "sbg/lutcover.hpp"
 #include "sbg/rng.hpp"
-
-// Host-side check of a HIP runtime call, used by both .hip files.
-#define SBG_HIP_CHECK(expr)                                                    \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      throw std::runtime_error(std::string("HIP error: ") +                    \
-                               hipGetErrorString(_e) + " at " #expr);          \
-    }                                                                          \
-  } while (0)
+#include "scan_types.hpp"
 
 namespace sbg {
 namespace {
-
-// ---------------------------------------------------------------------------
-// Device-side control block.
-// ---------------------------------------------------------------------------
-struct DevCtl {
-  u32 abort;
-  u32 lock;
-  u32 found;
-  u32 pool_n;  // ordered k=7: the pool size, for k_scan7_assign's ranks
-  u16 res[10];
-  u16 pad2[3];
-  unsigned long long evaluated;
-  unsigned long long queue;      // prefix dequeue counter
-  unsigned long long hit_count;  // K7 filter
-  u32 overflow;                  // K7 filter: hit buffer overflowed
-  u32 pad3;
-  // k=2: minimum over the hits of rank << 8 | matcher entry. Ordered scans
-  // (ScanRequest::ordered) of the other kinds: minimum over the hits of
-  // rank << 16 | function << 8 | argument order (k=3 and k=4; k=3 leaves the
-  // low 16 bits zero) or of the plain rank (k=5, k=7, shared-input). The
-  // host, or the service leader, sets it to all-ones before every request.
-  unsigned long long best;
-};
-
-// Shift of the rank inside DevCtl::best for ordered k=3 / k=4 scans.
-constexpr int BEST3_SHIFT = 16;
-
-struct Hit7 {
-  u64 p1[2];
-  u64 p0[2];
-  u16 nums[7];
-  u16 pad;
-};
 
 // Closed-form binomials; constant divisors compile to multiply-high.
 __device__ __forceinline__ i64 cf2(i64 x) { return x < 2 ? 0 : x * (x - 1) / 2; }
@@ -227,51 +181,6 @@ __device__ __forceinline__ i64 dev_rank7(const u16* ids, int n) {
   return r + (ids[6] - ids[5] - 1);
 }
 
-// What a k=2 request carries besides the pool: the pair matcher and the
-// visit order (order[j] < n for j < n; the tail is never read). Sized in
-// whole u64 words so that it is copied and staged 8 bytes at a time.
-struct Pair2Stage {
-  u8 matcher[256];
-  u16 order[(MAX_GATES + 3) / 4 * 4];
-};
-static_assert(sizeof(Pair2Stage) % 8 == 0);
-
-// A k=2 request must name its matcher, and its order must stay inside the
-// pool: the kernels index the LDS pool with it unchecked.
-inline void check_pair2_request(const ScanRequest& rq) {
-  if (rq.matcher2 == nullptr) throw std::runtime_error("scan2 needs matcher2");
-  if (rq.n > MAX_GATES) throw std::runtime_error("scan2: pool too large");
-  if (rq.order == nullptr) return;
-  for (int j = 0; j < rq.n; j++) {
-    if (rq.order[j] >= rq.n) throw std::runtime_error("scan2: order out of range");
-  }
-}
-
-inline void fill_pair2_stage(Pair2Stage* out, const ScanRequest& rq) {
-  std::memcpy(out->matcher, rq.matcher2->entry, sizeof(out->matcher));
-  for (int j = 0; j < rq.n; j++) {
-    out->order[j] = rq.order != nullptr ? rq.order[j] : static_cast<u16>(j);
-  }
-}
-
-struct ScanArgs {
-  const ttable* pool;  // device pool (n tables)
-  DevCtl* ctl;
-  Hit7* hits;          // K7 only
-  u64 hit_cap;         // K7 only
-  const Avail3Matcher* matcher;  // k=4 only
-  const Pair2Stage* pair2;       // k=2 only
-  ttable T1, T0;
-  int n;
-  i64 begin, end;
-  u64 excl;  // excluded gate ids < 64
-  u64 seed;
-  int count_all;
-  int slices7;  // K7: sub-quad slicing factor (dequeue unit = quad x slice)
-};
-
-constexpr int SCAN_BLOCK = 256;
-
 // LDS pool stride: 6 u64 (48 B) per gate instead of 4 (32 B). A 32 B
 // stride puts ds_read_b128 lane groups on 8-way-conflicting banks when
 // lanes read consecutive gate ids; 48 B (12 dwords, 16 B aligned) spreads
@@ -291,299 +200,6 @@ __device__ __forceinline__ void load_pool_lds(u64* s_pool, const ttable* pool,
   for (int i = threadIdx.x; i < n * 4; i += blockDim.x) {
     s_pool[(i >> 2) * STR + (i & 3)] = src[i];
   }
-}
-
-// ---------------------------------------------------------------------------
-// Gate-transposed pool. G[p][W], p a truth-table position and W a 32-gate
-// word: bit i of G[p][W] is bit p of the gate with shifted id 32 W + i,
-// i.e. of gate 32 W + i - pad (0 where that is no gate of the pool). The
-// caller chooses pad so that the pool's last gate ends a word group (see
-// sbg/scan5_geom.hpp); n + pad <= 32 GT_WORDS. One
-// dword then holds one table position of 32 candidates' last gate, and a
-// cell test over those candidates costs a few instructions per position of
-// the cell instead of a pass over whole 256-bit tables per candidate.
-// ---------------------------------------------------------------------------
-constexpr int GT_WORDS = (MAX_GATES + 31) / 32;  // dwords per position
-constexpr int GT_DWORDS = 256 * GT_WORDS;
-
-// 16- and 8-byte LDS reads of u64 / u32 arrays through another type
-// (may_alias makes the differently-typed read well defined).
-typedef u32 lds_u32x4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
-typedef u32 lds_u32x2 __attribute__((ext_vector_type(2), may_alias, aligned(8)));
-typedef u32 lds_u32 __attribute__((may_alias));
-
-// Cooperative build of G in LDS from the row-form pool staged at stride STR
-// (call after the barrier that publishes s_pool; the caller places the one
-// that publishes s_G). A wave takes 64 gates and one 32-position table
-// word at a time: lane = gate, one ballot per position, lane b keeps
-// position b's 64 gate bits and stores them as two dwords.
-template <int STR>
-__device__ __forceinline__ void build_gate_transposed_lds(u32* s_G,
-                                                          const u64* s_pool,
-                                                          int n, int pad) {
-  const int lane = threadIdx.x & 63;
-  const int nwaves = blockDim.x >> 6;
-  const int items = ((n + pad + 63) >> 6) * 8;  // (64-id chunk, table word)
-  for (int item = threadIdx.x >> 6; item < items; item += nwaves) {
-    const int chunk = item >> 3, w = item & 7;
-    const int gate = chunk * 64 + lane - pad;
-    u32 row = 0;
-    if (gate >= 0 && gate < n) {
-      row = reinterpret_cast<const lds_u32*>(&s_pool[gate * STR])[w];
-    }
-    u32 lo = 0, hi = 0;
-#pragma unroll
-    for (int b = 0; b < 32; b++) {
-      const u64 bal = __ballot((row >> b) & 1u);
-      if (lane == b) {
-        lo = static_cast<u32>(bal);
-        hi = static_cast<u32>(bal >> 32);
-      }
-    }
-    if (lane < 32) {
-      u32* dst = &s_G[(w * 32 + lane) * GT_WORDS + 2 * chunk];
-      dst[0] = lo;
-      dst[1] = hi;
-    }
-  }
-}
-
-// A value that every lane of the wave holds alike, as a scalar.
-__device__ __forceinline__ u32 dev_uniform(u32 v) {
-  return static_cast<u32>(
-      __builtin_amdgcn_readfirstlane(static_cast<int>(v)));
-}
-
-// G[p][W .. W + NW) for NW in {1, 2}, W even when NW == 2; gw = &G[0][W].
-template <int NW>
-struct GtWords {
-  u32 w[NW];
-};
-template <int NW>
-__device__ __forceinline__ GtWords<NW> gt_load(const u32* gw, u32 p) {
-  static_assert(NW == 1 || NW == 2);
-  GtWords<NW> g;
-  if constexpr (NW == 1) {
-    g.w[0] = gw[p * GT_WORDS];
-  } else {
-    const lds_u32x2 v = *reinterpret_cast<const lds_u32x2*>(&gw[p * GT_WORDS]);
-    g.w[0] = v.x;
-    g.w[1] = v.y;
-  }
-  return g;
-}
-
-// (a & b) | acc in one VALU instruction. Written out because the compiler
-// rebalances a plain C chain of these into v_and_b32 pairs feeding
-// v_or3_b32 (11 instructions per 8-dword reduction instead of 8) and keeps
-// vectorized copies of the loop-invariant operands.
-__device__ __forceinline__ u32 dev_and_or(u32 a, u32 b, u32 acc) {
-  u32 r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc));
-  return r;
-}
-
-// (a & ~b) | acc, likewise one instruction (gfx950's three-input bit op,
-// truth table 0xba), so ~b is never materialised.
-__device__ __forceinline__ u32 dev_andn_or(u32 a, u32 b, u32 acc) {
-  u32 r;
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba"
-      : "=v"(r) : "v"(a), "v"(b), "v"(acc));
-  return r;
-}
-
-// (~a & ~b) | acc (truth table 0xab).
-__device__ __forceinline__ u32 dev_nor_or(u32 a, u32 b, u32 acc) {
-  u32 r;
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xab"
-      : "=v"(r) : "v"(a), "v"(b), "v"(acc));
-  return r;
-}
-
-// The positions of one forced side (target-1 or target-0) of a cell, seen
-// by 32 NW candidates (x, e) at once, e the word's gates: per quadrant
-// (x's bit, e's bit) the candidates that have one of the side's positions
-// there.
-template <int NW>
-struct GtSide {
-  u32 q11[NW] = {}, q10[NW] = {}, q01[NW] = {}, q00[NW] = {};
-};
-
-// One position: g = G[p][W ..], m = all-ones where the lane's own gate x
-// has bit p set, else 0.
-template <int NW>
-__device__ __forceinline__ void gt_accumulate(GtSide<NW>& s,
-                                              const GtWords<NW>& g, u32 m) {
-#pragma unroll
-  for (int k = 0; k < NW; k++) {
-    s.q11[k] = dev_and_or(g.w[k], m, s.q11[k]);
-    s.q10[k] = dev_andn_or(m, g.w[k], s.q10[k]);
-    s.q01[k] = dev_andn_or(g.w[k], m, s.q01[k]);
-    s.q00[k] = dev_nor_or(g.w[k], m, s.q00[k]);
-  }
-}
-
-// Position lists of a cell's two forced sides, for gt_screen: the
-// side's positions in ascending order as bytes, padded to a multiple of
-// GT_LIST_STEP by repeating the last one (accumulating a position twice
-// changes nothing). The target-1 list starts at byte 0, the target-0 list
-// at the next multiple of 16; both are read 16 bytes at a time. The first
-// GT_HEAD_BYTES of each list are filed a second time, side by side (target-1
-// at byte 0, target-0 at byte GT_HEAD_BYTES of `head`), for a reader that
-// wants them next to its other per-cell data; bytes past a list's padded
-// length are left as they were.
-constexpr int GT_LIST_STEP = 4;
-constexpr int GT_LIST_BYTES = 256 + 2 * 16;
-constexpr int GT_HEAD_BYTES = 16;
-
-// Called by 32 threads, part = 0..31, each filing the 8 positions of byte
-// `part` of the cell's forced sets (h1, h0: 4 words each, disjoint).
-// counts[0], counts[1]: the lists' padded lengths; counts[2]: the target-0
-// list's byte offset.
-__device__ __forceinline__ void gt_build_lists(const u64* h1, const u64* h0,
-                                               u8* list, u8* head,
-                                               int* counts, int part) {
-  const int wd = part >> 3, sh = (part & 7) * 8;
-  int base = 0;
-  for (int side = 0; side < 2; side++) {
-    const u64* h = side == 0 ? h1 : h0;
-    int total = 0, at = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int c = __popcll(h[k]);
-      total += c;
-      if (k < wd) at += c;
-    }
-    at += __popcll(h[wd] & ((1ULL << sh) - 1));
-    const int padded = (total + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1);
-    u32 mine = static_cast<u32>(h[wd] >> sh) & 0xffu;
-    if (mine != 0) {
-      int p = 0;
-      for (; mine != 0; mine &= mine - 1) {
-        p = part * 8 + __ffs(mine) - 1;
-        if (at < GT_HEAD_BYTES) {
-          head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
-        }
-        list[base + at++] = static_cast<u8>(p);
-      }
-      if (at == total) {  // the side's last position is here: pad with it
-        for (; at < padded; at++) {
-          if (at < GT_HEAD_BYTES) {
-            head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
-          }
-          list[base + at] = static_cast<u8>(p);
-        }
-      }
-    }
-    if (part == 0) counts[side] = padded;
-    base = (total + 15) & ~15;
-    if (part == 0 && side == 0) counts[2] = base;
-  }
-}
-
-// Candidates of word k in whose cell some quadrant holds both target-1 and
-// target-0 positions: no function of (cell, x, e) realises the target.
-template <int NW>
-__device__ __forceinline__ u32 gt_conflict(const GtSide<NW>& s1,
-                                           const GtSide<NW>& s0, int k) {
-  u32 c = s1.q11[k] & s0.q11[k];
-  c = dev_and_or(s1.q10[k], s0.q10[k], c);
-  c = dev_and_or(s1.q01[k], s0.q01[k], c);
-  return dev_and_or(s1.q00[k], s0.q00[k], c);
-}
-
-// GT_LIST_STEP listed positions, the bytes of pw.
-template <int NW>
-__device__ __forceinline__ void gt_accumulate_step(GtSide<NW>& s, u32 pw,
-                                                   const u32* gw,
-                                                   const u32* gx, u32 xbit) {
-#pragma unroll
-  for (int i = 0; i < GT_LIST_STEP; i++) {
-    const u32 p = (pw >> (8 * i)) & 0xffu;
-    const GtWords<NW> g = gt_load<NW>(gw, p);
-    const u32 m = static_cast<u32>(
-        __builtin_amdgcn_sbfe(static_cast<int>(gx[p * GT_WORDS]), xbit, 1));
-    gt_accumulate<NW>(s, g, m);
-  }
-}
-
-// Screen the candidates `valid` of a wave's lanes against one cell, given
-// as its two position lists (n1, n0: padded lengths; lists and lengths
-// wave-uniform). gw = &G[0][W] of the lane's candidate words; x's bits
-// come out of G as well: gx = &G[0][x >> 5], xbit = x & 31. Returns the
-// candidates without a conflict. The lists are walked side by side,
-// GT_LIST_STEP positions of each at a time, and the walk ends as soon as
-// no lane of the wave has a candidate left: a few positions of either side
-// already contradict nearly every candidate (sampled on the benchmark
-// pool: of 60000, 1518 passed the first 4 of each side, 69 the first 6, 3
-// the first 8 and none the first 12, against 104 positions in the cell), so
-// the cost follows that number and not the cell's size. The list bytes go through
-// SGPRs; only the G reads, the bit extract and the accumulation are
-// vector work. head1, head0: the lists' first GT_HEAD_BYTES, already in
-// scalars (gt_build_lists' `head`), so that the first G reads wait for no
-// list read. Call from code that the whole wave runs together.
-template <int NW>
-__device__ __forceinline__ GtWords<NW> gt_screen(const u32 (&head1)[4],
-                                                 const u32 (&head0)[4],
-                                                 const u8* list1, int n1,
-                                                 const u8* list0, int n0,
-                                                 const u32* gw, const u32* gx,
-                                                 u32 xbit,
-                                                 const GtWords<NW>& valid) {
-  static_assert(GT_LIST_STEP == 4);  // one dword of list bytes per step
-  static_assert(GT_HEAD_BYTES == 16);  // one pass of the loop below
-  GtWords<NW> pend = valid;
-  // An empty side cannot contradict: everything passes.
-  if (n1 == 0 || n0 == 0) return pend;
-  GtSide<NW> s1, s0;
-  const int nmax = n1 > n0 ? n1 : n0;
-  const auto remaining = [&]() {
-    u32 left = 0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      pend.w[w] = valid.w[w] & ~gt_conflict<NW>(s1, s0, w);
-      left |= pend.w[w];
-    }
-    return left;
-  };
-  for (int k = 0; k < nmax; k += 16) {
-    u32 pw1[4] = {}, pw0[4] = {};
-    if (k == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        pw1[j] = head1[j];
-        pw0[j] = head0[j];
-      }
-    } else {
-      if (k < n1) {
-        const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list1 + k);
-        pw1[0] = __builtin_amdgcn_readfirstlane(v.x);
-        pw1[1] = __builtin_amdgcn_readfirstlane(v.y);
-        pw1[2] = __builtin_amdgcn_readfirstlane(v.z);
-        pw1[3] = __builtin_amdgcn_readfirstlane(v.w);
-      }
-      if (k < n0) {
-        const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list0 + k);
-        pw0[0] = __builtin_amdgcn_readfirstlane(v.x);
-        pw0[1] = __builtin_amdgcn_readfirstlane(v.y);
-        pw0[2] = __builtin_amdgcn_readfirstlane(v.z);
-        pw0[3] = __builtin_amdgcn_readfirstlane(v.w);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int kk = k + GT_LIST_STEP * j;
-      if (kk >= nmax) break;
-      if (kk < n1) gt_accumulate_step<NW>(s1, pw1[j], gw, gx, xbit);
-      if (kk < n0) gt_accumulate_step<NW>(s0, pw0[j], gw, gx, xbit);
-      // No test after the first step: 4 positions a side still let
-      // 2.5% through, and a wave holds thousands of candidates.
-      if (kk == 0) continue;
-      if (!__any(remaining() != 0)) return pend;
-    }
-  }
-  remaining();
-  return pend;
 }
 
 // Stage the k=4 function matcher: bitmap, function list and count.

@@ -1,7 +1,8 @@
 // gpu.hpp — single-GPU scan engine: CDNA4 (gfx950) HIP kernels for the
 // 3/5/7-LUT and shared-input two-LUT candidate scans and the gate-mode
-// triple (k=4) and pair (k=2) scans. Implementation: csrc/hip/scan_kernels.hip (one-shot kernels,
-// GpuEngine) and csrc/hip/scan_service.hip (persistent k=4 / k=2 service).
+// triple (k=4) and pair (k=2) scans. Implementation: csrc/hip/gpu_engine.hip
+// (GpuEngine), csrc/hip/scan_launch.hpp (one-shot kernels) and
+// csrc/hip/scan_service.hip (persistent k=4 / k=2 service).
 //
 // One GpuEngine owns one device (HIP_VISIBLE_DEVICES / torchrun LOCAL_RANK
 // selects which): multi-GPU runs use one process per GPU with RCCL-backed

@@ -118,6 +118,9 @@ PYBIND11_MODULE(_core, m) {
   m.attr("SCAN5_WIDE_MIN_ROW") = SCAN5_WIDE_MIN_ROW;
   m.def("gpu_available", &gpu_available);
   m.def("gpu_count", &gpu_count);
+  m.attr("SCAN5_WAVE_MIN_POOL") = SCAN5_WAVE_MIN_POOL;
+  m.def("scan5_wave_min_pool", &scan5_wave_min_pool);
+  m.def("set_scan5_wave_min_pool", &set_scan5_wave_min_pool);
 
   // --- ttable ops (bytes <-> 256-bit tables) ---
   m.def("generate_target", [](int bit, py::object sbox) {
@@ -210,6 +213,23 @@ PYBIND11_MODULE(_core, m) {
     return out;
   }, py::arg("n"), py::arg("c"), py::arg("lo"), py::arg("hi"),
      py::arg("excl") = 0);
+  // The chunks of k_scan5_wave's triple queue, (first, count) in the order
+  // of the chunk counter, up to the first empty one.
+  m.attr("SCAN5_CHUNK_MAX") = SCAN5_CHUNK_MAX;
+  m.attr("SCAN5_CHUNK_MIN") = SCAN5_CHUNK_MIN;
+  m.def("scan5_chunks", [](i64 units, int waves) {
+    if (units < 0 || waves < 1) {
+      throw std::invalid_argument("scan5_chunks: need units >= 0, waves >= 1");
+    }
+    const Scan5ChunkPlan plan = scan5_chunk_plan(units, waves);
+    py::list out;
+    for (i64 k = 0;; k++) {
+      const Scan5Chunk ch = scan5_chunk(plan, k);
+      if (ch.count == 0) break;
+      out.append(py::make_tuple(ch.first, ch.count));
+    }
+    return out;
+  }, py::arg("units"), py::arg("waves"));
 
   // --- lutcover primitives (for oracle tests) ---
   m.def("naive_check_n_lut_possible",

@@ -14,6 +14,7 @@
 #include "sbg/comb.hpp"
 #include "sbg/gpu.hpp"
 #include "sbg/lutcover.hpp"
+#include "sbg/scan5_geom.hpp"
 #include "scan_launch.hpp"
 #include "scan_service.hpp"
 
@@ -227,8 +228,20 @@ struct GpuEngine::Impl {
     i64 t_begin, t_last;
     prefix_rank_span(rq.n, shared ? 4 : 5, 3, args.begin, args.end, &t_begin,
                      &t_last);
+    const i64 units = t_last - t_begin + 1;
+    if (!shared && rq.n >= scan5_wave_min_pool()) {
+      // Large pools: the wide kernel whose waves own their triples. They
+      // take chunks of the triples [t_begin, t_begin + units), numbered from
+      // 0, at least SCAN5_CHUNK_MIN triples a wave.
+      h_ctl->queue = 0;
+      const int grid = queue_grid(units, SCAN5_CHUNK_MIN * (SCAN_BLOCK / 64));
+      round_trip([&] {
+        launch_scan5_wave(ordered, grid, stream, args, t_begin, units);
+      });
+      return;
+    }
     h_ctl->queue = static_cast<unsigned long long>(t_begin);
-    const int grid = queue_grid(t_last - t_begin + 1, shared ? SB : TB);
+    const int grid = queue_grid(units, shared ? SB : TB);
     // k=5: pools without a row longer than the crossover never take the wide
     // walk: they get the variant that has no transposed pool to build.
     const ScanKernel which =
@@ -322,6 +335,10 @@ struct GpuEngine::Impl {
 };
 
 bool gpu_available() { return gpu_count() > 0; }
+
+static int g_scan5_wave_min_pool = SCAN5_WAVE_MIN_POOL;
+int scan5_wave_min_pool() { return g_scan5_wave_min_pool; }
+void set_scan5_wave_min_pool(int n) { g_scan5_wave_min_pool = n; }
 
 int gpu_count() {
   int count = 0;

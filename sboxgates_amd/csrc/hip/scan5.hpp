@@ -1,6 +1,7 @@
 // scan5.hpp — the 5-LUT scan kernel k_scan5 with what only it uses: the
 // gate-transposed pool and its per-position cell test (gt_*), the survivor
-// routine and the wide walk. Included by the kernel modules only
+// routine, the wide walk and its wave-owned variant k_scan5_wave. Included
+// by the kernel modules only
 // (scan_launch.hpp).
 #pragma once
 
@@ -63,12 +64,6 @@ __device__ __forceinline__ void build_gate_transposed_lds(u32* s_G,
       dst[1] = hi;
     }
   }
-}
-
-// A value that every lane of the wave holds alike, as a scalar.
-__device__ __forceinline__ u32 dev_uniform(u32 v) {
-  return static_cast<u32>(
-      __builtin_amdgcn_readfirstlane(static_cast<int>(v)));
 }
 
 // G[p][W .. W + NW) for NW in {1, 2}, W even when NW == 2; gw = &G[0][W].
@@ -827,6 +822,363 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
   }
 
   block_add_evaluated(ctl, local_eval);
+}
+
+// gt_build_lists by one whole wave, both sides at once, lane = 32 side +
+// part: each lane files the 8
+// positions of byte `part` of its side of the cell's forced sets (h1, h0: 4
+// words each, disjoint). Returns the lists' padded lengths and the target-0
+// list's byte offset, 10 bits each, the same in every lane.
+__device__ __forceinline__ u32 gt_build_lists_wave(const u64* h1,
+                                                   const u64* h0, u8* list,
+                                                   u8* head, int lane) {
+  const int side = lane >> 5, part = lane & 31;
+  const int wd = part >> 3, sh = (part & 7) * 8;
+  const u64* h = side == 0 ? h1 : h0;
+  int total1 = 0, total0 = 0, at = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int c1 = __popcll(h1[k]), c0 = __popcll(h0[k]);
+    total1 += c1;
+    total0 += c0;
+    if (k < wd) at += side == 0 ? c1 : c0;
+  }
+  const u64 hw = h[wd];
+  at += __popcll(hw & ((1ULL << sh) - 1));
+  const int total = side == 0 ? total1 : total0;
+  const int off0 = (total1 + 15) & ~15;
+  const int base = side == 0 ? 0 : off0;
+  const int padded = (total + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1);
+  u32 mine = static_cast<u32>(hw >> sh) & 0xffu;
+  if (mine != 0) {
+    int p = 0;
+    for (; mine != 0; mine &= mine - 1) {
+      p = part * 8 + __ffs(mine) - 1;
+      if (at < GT_HEAD_BYTES) {
+        head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
+      }
+      list[base + at++] = static_cast<u8>(p);
+    }
+    if (at == total) {  // the side's last position is here: pad with it
+      for (; at < padded; at++) {
+        if (at < GT_HEAD_BYTES) {
+          head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
+        }
+        list[base + at] = static_cast<u8>(p);
+      }
+    }
+  }
+  const u32 n1 =
+      static_cast<u32>((total1 + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1));
+  const u32 n0 =
+      static_cast<u32>((total0 + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1));
+  return n1 | (n0 << 10) | (static_cast<u32>(off0) << 20);
+}
+
+
+// ---------------------------------------------------------------------------
+// k_scan5_wave: a wave owns its triples. The block stages the pool and
+// builds G once; from then on its waves run on their own and meet again
+// only to add up `evaluated`. A wave takes a chunk of consecutive triples
+// off the queue with one atomic (sbg/scan5_geom.hpp has the chunk rule),
+// decodes them one per lane, and for every live triple builds the prefix
+// cells, picks the screen cell, lists its positions and walks the
+// triple's tasks, all in a slice of LDS that only this wave touches. What
+// the walk needs of the triple stays in scalars for the whole triple.
+// ---------------------------------------------------------------------------
+
+// A wave's private LDS: the current triple's prefix cells (the rare path
+// reads them), the screen cell's position lists and their heads, and the
+// prefix's gate ids for the survivor routine.
+struct alignas(16) Scan5WaveSlice {
+  u64 H1[8][4];
+  u64 H0[8][4];
+  u8 pos[GT_LIST_BYTES];
+  u32 head[2 * GT_HEAD_BYTES / 4];
+  u16 abc[8];  // 3 used
+};
+
+typedef __attribute__((address_space(3))) const Scan5WaveSlice lds_cslice;
+
+// Set in scan5_wave_walk's result: the scan was aborted, the wave stops.
+constexpr u64 SCAN5_WALK_ABORTED = 1ULL << 63;
+
+// Walk of one triple by one wave: returns the pairs this lane evaluated.
+// The triple's values arrive as the same number in every lane and go
+// through scalars here: its last gate c, its pair window [lo, hi), its flat
+// rank base, the position lists' padded lengths and the target-0 list's
+// offset (10 bits each in `lens`), the live cells and the screen cell << 8
+// (`cells`). Not inlined: inside the kernel this loop's invariants were
+// spilled and reloaded from scratch in every step; as a function it gets
+// registers of its own.
+template <int STR, bool ORD>
+__device__ __attribute__((noinline)) u64 scan5_wave_walk(
+    const ScanArgs& args, DevCtl* ctl, int pad, lds_cu64* l_pool,
+    lds_cu32* l_G, lds_cslice* l_slice, int c_, int lo_, int hi_, i64 base_,
+    u32 lens_, u32 cells_) {
+  constexpr int NW = SCAN5_WIDE_WORDS;
+  constexpr int GB = SCAN5_WIDE_GB;
+  static_assert(GB == 64);  // a lane a row
+  const u64* s_pool = (const u64*)l_pool;
+  const u32* s_G = (const u32*)l_G;
+  const Scan5WaveSlice* sl = (const Scan5WaveSlice*)l_slice;
+  const int lane = threadIdx.x & 63;
+  const int n = args.n;
+  const int count_all = args.count_all;
+  const u64 excl = args.excl;
+  const int c = static_cast<int>(dev_uniform(c_));
+  const int lo = static_cast<int>(dev_uniform(lo_));
+  const int hi = static_cast<int>(dev_uniform(hi_));
+  const i64 base = static_cast<i64>(
+      static_cast<u64>(dev_uniform(static_cast<u32>(base_))) |
+      static_cast<u64>(dev_uniform(static_cast<u32>(base_ >> 32))) << 32);
+  const u32 lens = dev_uniform(lens_), cells = dev_uniform(cells_);
+  const int n1 = static_cast<int>(lens & 0x3ffu);
+  const int n0 = static_cast<int>((lens >> 10) & 0x3ffu);
+  const u8* list0 = sl->pos + (lens >> 20);
+  const u32 live = cells & 0xffu;
+  const int u0 = static_cast<int>(cells >> 8);
+  u64 local_eval = 0;
+  const lds_u32x4 rh1 = *reinterpret_cast<const lds_u32x4*>(&sl->head[0]);
+  const lds_u32x4 rh0 = *reinterpret_cast<const lds_u32x4*>(
+      &sl->head[GT_HEAD_BYTES / 4]);
+  const u32 head1[4] = {dev_uniform(rh1.x), dev_uniform(rh1.y),
+                        dev_uniform(rh1.z), dev_uniform(rh1.w)};
+  const u32 head0[4] = {dev_uniform(rh0.x), dev_uniform(rh0.y),
+                        dev_uniform(rh0.z), dev_uniform(rh0.w)};
+
+  // Walk. A task is (row d, word group): the pairs (d, e) with e among
+  // the GB gates of G's words [NW wg, NW wg + NW). The tasks run through
+  // the groups from the last one down, consecutive rows on consecutive
+  // lanes, 64 tasks a step: (wg, row0) is the step's first task, and a
+  // lane whose row lies past the group's end is in the next group down
+  // (which has 64 rows fewer, or is the triple's last).
+  const Scan5WideGroups g = scan5_wide_groups(n, pad, c);
+  int wg = g.w_max, rows = n - 2 - c, row0 = 0;
+  while (wg >= g.w_min) {
+    // Unordered first-hit scans poll once per step, as often per pair
+    // walked as the tasks of the batch walk did.
+    if (!ORD && !count_all && wave_abort(ctl)) {
+      return local_eval | SCAN5_WALK_ABORTED;
+    }
+    const int rows_down = scan5_wide_rows(pad, c, wg - 1);
+    int d2 = row0 + lane, lwg = wg;
+    bool mine = true;
+    if (d2 >= rows) {
+      d2 -= rows;
+      lwg = wg - 1;
+      mine = lwg >= g.w_min && d2 < rows_down;
+    }
+    if (!mine) {  // no task: any address inside G will do
+      d2 = 0;
+      lwg = wg;
+    }
+    // Bit i of the task is the pair (d, e0 + i), flat index q0 + i;
+    // valid: clipped to e > d and to the triple's [lo, hi) window,
+    // without the excluded gates.
+    const Scan5WideTask wt = scan5_wide_task_at(n, pad, c, lwg, d2);
+    const u64 valid = mine ? scan5_wide_valid(wt, lo, hi, excl) : 0;
+    row0 += 64;
+    while (wg >= g.w_min && row0 >= rows) {
+      row0 -= rows;
+      wg--;
+      rows = scan5_wide_rows(pad, c, wg);
+    }
+    if (!__any(valid != 0)) continue;
+    local_eval += __popcll(valid);
+
+    // Screen: the listed positions of the screen cell. Per position the
+    // lanes read G at their candidate words (the same address across
+    // most of a wave: LDS broadcast) and at d's own word for td's bit.
+    GtWords<NW> vw;
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+      vw.w[w] = static_cast<u32>(valid >> (32 * w));
+    }
+    const GtWords<NW> pw = gt_screen<NW>(
+        head1, head0, sl->pos, n1, list0, n0, &s_G[NW * wt.wg],
+        &s_G[(wt.d + pad) >> 5], (wt.d + pad) & 31, vw);
+    u64 pend = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+      pend |= static_cast<u64>(pw.w[w]) << (32 * w);
+    }
+
+    // Rare path. The screen only ever passes too much.
+    while (pend != 0) {
+      const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
+      pend &= pend - 1;
+      scan5_after_screen<STR, ORD>(args, ctl, s_pool, sl->H1, sl->H0,
+                                   sl->abc, live & ~(1u << u0),
+                                   base + wt.q0 + i, wt.d, wt.e0 + i);
+    }
+  }
+  return local_eval;
+}
+
+// q_begin, q_units: the first triple of the queue and the number of triples
+// in it; ctl->queue counts chunks of them, from 0.
+template <bool ORD>
+__device__ __forceinline__ void scan5_wave_scan(const ScanArgs& args,
+                                                i64 q_begin, i64 q_units) {
+  constexpr int STR = PSTR_DENSE;
+  static_assert(SCAN5_CHUNK_MAX == 64);  // a lane a triple
+  __shared__ alignas(16) u64 s_pool[MAX_GATES * STR];
+  __shared__ alignas(16) u32 s_G[GT_DWORDS];
+  __shared__ Scan5WaveSlice s_slice[SCAN_BLOCK / 64];
+  __shared__ u64 s_T[2][4];  // T1, T0: lanes index them by their own dword
+
+  const int n = args.n;
+  const int pad = scan5_wide_pad(n);  // shift of the gate ids inside G
+  load_pool_lds<STR>(s_pool, args.pool, n);
+  if (threadIdx.x == 0) {
+    for (int w = 0; w < 4; w++) {
+      s_T[0][w] = args.T1.w[w];
+      s_T[1][w] = args.T0.w[w];
+    }
+  }
+  __syncthreads();
+  build_gate_transposed_lds<STR>(s_G, s_pool, n, pad);
+  __syncthreads();
+
+  DevCtl* ctl = args.ctl;
+  const int lane = threadIdx.x & 63;
+  Scan5WaveSlice* sl = &s_slice[threadIdx.x >> 6];
+  const int count_all = args.count_all;
+  const i64 total3 = cf3(n);
+  const Scan5ChunkPlan plan = scan5_chunk_plan(
+      q_units, static_cast<int>(gridDim.x) * (SCAN_BLOCK / 64));
+  // Cell build: lane = (cell u, dword dw) of the 8 cells x 8 dwords a side;
+  // cells on the low lane bits, so that lanes 0..7 speak for the 8 cells.
+  const int cu = lane & 7, cdw = lane >> 3;
+  const lds_u32* pool32 = reinterpret_cast<const lds_u32*>(s_pool);
+  const u32 T1d = reinterpret_cast<const lds_u32*>(s_T[0])[cdw];
+  const u32 T0d = reinterpret_cast<const lds_u32*>(s_T[1])[cdw];
+  u64 local_eval = 0;
+
+  for (bool done = false; !done;) {
+    // Dequeue: one lane, one atomic per chunk. Ordered: a known hit takes
+    // the abort flag's place; chunks come in increasing triple order, so
+    // every chunk not yet taken ranks above any hit already known.
+    int k_lo = 0, k_hi = 0;
+    if (lane == 0) {
+      const bool halt =
+          !count_all && (ORD ? dev_best(ctl) != ~0ULL : dev_abort(ctl));
+      const i64 k = halt ? -1
+                         : static_cast<i64>(__hip_atomic_fetch_add(
+                               &ctl->queue, 1ULL, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT));
+      k_lo = static_cast<int>(k);
+      k_hi = static_cast<int>(k >> 32);
+    }
+    const i64 k = static_cast<i64>(
+        static_cast<u64>(dev_uniform(static_cast<u32>(k_lo))) |
+        static_cast<u64>(dev_uniform(static_cast<u32>(k_hi))) << 32);
+    if (k < 0) break;
+    const Scan5Chunk ch = scan5_chunk(plan, k);
+    if (ch.count == 0) break;
+
+    // Lane i decodes triple i of the chunk and clips its pair window.
+    PrefixWindow<3> p;
+    if (lane < ch.count) {
+      p = decode_prefix_window<3>(q_begin + ch.first + lane, total3, args);
+      drop_dead_prefix(p, args);
+    }
+    const int v_ab = p.ids[0] | (p.ids[1] << 16);
+    const int v_c = p.ids[2];
+    const int v_lo = static_cast<int>(p.lo);  // <= C(m, 2) < 2^17
+    const int v_hi = static_cast<int>(p.hi);
+    const int v_base_lo = static_cast<int>(p.base);
+    const int v_base_hi = static_cast<int>(p.base >> 32);
+
+    for (u64 todo = __ballot(p.lo < p.hi); todo != 0 && !done;
+         todo &= todo - 1) {
+      const int j = __ffsll(static_cast<unsigned long long>(todo)) - 1;
+      const int ab = wave_lane_value(v_ab, j);
+      const int a = ab & 0xffff, b = ab >> 16;
+      const int c = wave_lane_value(v_c, j);
+      const int lo = wave_lane_value(v_lo, j);
+      const int hi = wave_lane_value(v_hi, j);
+      const i64 base = static_cast<i64>(
+          static_cast<u64>(static_cast<u32>(wave_lane_value(v_base_lo, j))) |
+          static_cast<u64>(static_cast<u32>(wave_lane_value(v_base_hi, j)))
+              << 32);
+      // Ordered: ranks rise with the triple index, so a triple that begins
+      // above the best hit known ends this wave's scan. A triple it has
+      // begun runs to its end.
+      if constexpr (ORD) {
+        if (!count_all && static_cast<u64>(base) > wave_best(ctl)) {
+          done = true;
+          break;
+        }
+      }
+
+      // The eight prefix cells, masked with target-1 / target-0.
+      u32 cell = ~0u;
+      {
+        const u32 ra = pool32[a * (2 * STR) + cdw];
+        const u32 rb = pool32[b * (2 * STR) + cdw];
+        const u32 rc = pool32[c * (2 * STR) + cdw];
+        cell &= (cu & 4) ? ra : ~ra;
+        cell &= (cu & 2) ? rb : ~rb;
+        cell &= (cu & 1) ? rc : ~rc;
+      }
+      const u32 h1 = cell & T1d, h0 = cell & T0d;
+      reinterpret_cast<lds_u32*>(&sl->H1[0][0])[cu * 8 + cdw] = h1;
+      reinterpret_cast<lds_u32*>(&sl->H0[0][0])[cu * 8 + cdw] = h0;
+      if (lane == 0) {
+        sl->abc[0] = static_cast<u16>(a);
+        sl->abc[1] = static_cast<u16>(b);
+        sl->abc[2] = static_cast<u16>(c);
+      }
+      // Sizes of the cell's two sides (at most 256 each), summed over its
+      // dwords. A cell with an empty side cannot contradict: only the
+      // others are live. The screen runs on the live cell whose smaller
+      // side is largest, ties to the lower cell (on the benchmark pool the
+      // lowest live cell lets ~1.6% of candidates through, this one ~none);
+      // cell 7 when none is live.
+      u32 sizes = static_cast<u32>(__popc(h1)) |
+                  (static_cast<u32>(__popc(h0)) << 16);
+      sizes += __shfl_xor(sizes, 8);
+      sizes += __shfl_xor(sizes, 16);
+      sizes += __shfl_xor(sizes, 32);
+      const u32 c1 = sizes & 0xffffu, c0 = sizes >> 16;
+      const bool cell_live = c1 != 0 && c0 != 0;
+      const u32 live = static_cast<u32>(__ballot(cell_live)) & 0xffu;
+      u32 key = cell_live
+                    ? ((c1 < c0 ? c1 : c0) << 3) | static_cast<u32>(7 - cu)
+                    : 0u;
+      key = max(key, static_cast<u32>(__shfl_xor(key, 1)));
+      key = max(key, static_cast<u32>(__shfl_xor(key, 2)));
+      key = max(key, static_cast<u32>(__shfl_xor(key, 4)));
+      const int u0 = 7 - static_cast<int>(dev_uniform(key) & 7u);
+      wave_lds_sync();
+
+      // The screen cell's position lists and their heads.
+      const u32 lens = dev_uniform(gt_build_lists_wave(
+          sl->H1[u0], sl->H0[u0], sl->pos, reinterpret_cast<u8*>(sl->head),
+          lane));
+      wave_lds_sync();
+      const u64 r = scan5_wave_walk<STR, ORD>(
+          args, ctl, pad, (lds_cu64*)s_pool, (lds_cu32*)s_G, (lds_cslice*)sl,
+          c, lo, hi, base, lens, live | (static_cast<u32>(u0) << 8));
+      local_eval += r & ~SCAN5_WALK_ABORTED;
+      done = (r & SCAN5_WALK_ABORTED) != 0;
+      // The next triple overwrites the slice.
+      wave_lds_sync();
+    }
+  }
+
+  block_add_evaluated(ctl, local_eval);
+}
+
+// The wave-owned variant of k_scan5<true, ORD>, for the pools where it is
+// the faster one (the host chooses: SCAN5_WAVE_MIN_POOL). It walks every
+// triple on the gate-transposed pool, whatever its row length.
+template <bool ORD>
+__global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5_wave(
+    ScanArgs args, i64 q_begin, i64 q_units) {
+  scan5_wave_scan<ORD>(args, q_begin, q_units);
 }
 
 }  // namespace

@@ -169,6 +169,41 @@ __device__ __forceinline__ u64 dev_best(DevCtl* ctl) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---------------------------------------------------------------------------
+// Wave-level helpers of a scan whose waves run on their own (k_scan5_wave).
+// ---------------------------------------------------------------------------
+
+// A value that every lane of the wave holds alike, as a scalar.
+__device__ __forceinline__ u32 dev_uniform(u32 v) {
+  return static_cast<u32>(
+      __builtin_amdgcn_readfirstlane(static_cast<int>(v)));
+}
+
+// Orders a wave's LDS writes before its later LDS reads in other lanes.
+// One wave's LDS operations complete in issue order, so this only has to
+// keep the compiler from moving them and make it wait for the writes.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// Lane `src`'s value of v, src wave-uniform.
+__device__ __forceinline__ int wave_lane_value(int v, int src) {
+  return __builtin_amdgcn_readlane(v, src);
+}
+
+// dev_abort and dev_best for a whole wave, as scalars: the lanes read one
+// address and branch together.
+__device__ __forceinline__ bool wave_abort(const DevCtl* ctl) {
+  return dev_uniform(dev_abort(ctl) ? 1u : 0u) != 0;
+}
+__device__ __forceinline__ u64 wave_best(DevCtl* ctl) {
+  const u64 v = dev_best(ctl);
+  return static_cast<u64>(dev_uniform(static_cast<u32>(v))) |
+         static_cast<u64>(dev_uniform(static_cast<u32>(v >> 32))) << 32;
+}
+
 // Lexicographic rank of the ascending 7-combination ids of [0, n): the sum
 // decode_prefix_window starts, carried through all seven slots.
 __device__ __forceinline__ i64 dev_rank7(const u16* ids, int n) {

@@ -42,8 +42,11 @@
 // the default kernels then compile to exactly the code they had before there
 // was a second mode: with both instantiations in one module the optimizer
 // scheduled the default k_scan5 differently (same registers, same scratch,
-// 0.4% slower on the 5-LUT benchmark; profiles/ordered_scans.md §1). No
-// kernel is named outside those two modules.
+// 0.4% slower on the 5-LUT benchmark; profiles/ordered_scans.md §1). For the
+// same reason k_scan5_wave, in both modes, is a third module, scan_wave.hip:
+// with it in the other two, k_scan5 and scan5_wide_walk came out different
+// (they share the survivor routine with it). No kernel is named outside
+// those three modules.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -70,6 +73,12 @@ void launch_scan_default(ScanKernel which, int grid, hipStream_t stream,
 void launch_scan_ordered(ScanKernel which, int grid, hipStream_t stream,
                          const ScanArgs& args);
 
+// Launch k_scan5_wave on the queue of q_units triples from q_begin on.
+void launch_scan5_wave_default(int grid, hipStream_t stream,
+                               const ScanArgs& args, i64 q_begin, i64 q_units);
+void launch_scan5_wave_ordered(int grid, hipStream_t stream,
+                               const ScanArgs& args, i64 q_begin, i64 q_units);
+
 // Launch k_scan7_assign over nhits entries of the buffer `hits`; ctl is the
 // device control block, whose pool_n holds the pool size in the ordered mode.
 void launch_assign7_default(int grid, hipStream_t stream, const Hit7* hits,
@@ -82,6 +91,12 @@ inline void launch_scan(ScanKernel which, bool ordered, int grid,
                         hipStream_t stream, const ScanArgs& args) {
   (ordered ? launch_scan_ordered : launch_scan_default)(which, grid, stream,
                                                         args);
+}
+inline void launch_scan5_wave(bool ordered, int grid, hipStream_t stream,
+                              const ScanArgs& args, i64 q_begin,
+                              i64 q_units) {
+  (ordered ? launch_scan5_wave_ordered : launch_scan5_wave_default)(
+      grid, stream, args, q_begin, q_units);
 }
 inline void launch_assign7(bool ordered, int grid, hipStream_t stream,
                            const Hit7* hits, unsigned long long nhits,

@@ -22,6 +22,13 @@ namespace sbg {
 // time; shorter rows keep the 4-pair row segments. Pools of at most
 // SCAN5_WIDE_MIN_ROW + 3 gates therefore never reach the wide walk.
 constexpr int SCAN5_WIDE_MIN_ROW = 40;
+// 5-LUT scan: pools of at least this many gates run the wide kernel's
+// wave-owned variant (k_scan5_wave), which walks every triple on the
+// transposed pool and has no block barrier in its walk. Measured, full-range
+// scans: level with the batch kernel at 180 gates, 7 % less time at 220,
+// 17 % at 350 and 19 % at 450; more below (31 % at 120 gates, 53 % at 90), where
+// most triples have short rows and the per-triple set-up is all there is.
+constexpr int SCAN5_WAVE_MIN_POOL = 200;
 // 32-gate words of the transposed pool per wide task (1 or 2).
 constexpr int SCAN5_WIDE_WORDS = 2;
 
@@ -62,5 +69,11 @@ class GpuEngine {
 // True if the process can see at least one HIP device.
 bool gpu_available();
 int gpu_count();
+
+// The smallest pool that runs k_scan5_wave, SCAN5_WAVE_MIN_POOL unless set
+// otherwise; process-wide. For measuring the crossover and for tests that
+// run the wave-owned kernel on small pools.
+int scan5_wave_min_pool();
+void set_scan5_wave_min_pool(int n);
 
 }  // namespace sbg

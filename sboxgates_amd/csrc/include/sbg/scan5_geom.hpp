@@ -65,6 +65,21 @@ struct Scan5WideTask {
            // exist): bit i is the pair with flat index q0 + i
 };
 
+// The task of row d2 in group wg, for a walk that keeps (wg, d2) itself
+// (scan5_wide_decode finds them from a task index).
+SBG_GEOM_FN Scan5WideTask scan5_wide_task_at(int n, int pad, int c, int wg,
+                                             int d2) {
+  constexpr int GB = SCAN5_WIDE_GB;
+  const int m = n - 1 - c;
+  Scan5WideTask t;
+  t.wg = wg;
+  t.d2 = d2;
+  t.d = c + 1 + d2;
+  t.e0 = GB * wg - pad;
+  t.q0 = d2 * m - d2 * (d2 + 1) / 2 + t.e0 - t.d - 1;
+  return t;
+}
+
 // Task index -> task, 0 <= task < scan5_wide_task_count. Consecutive tasks
 // take consecutive rows of one group, last group first (it has the most
 // rows, so the search is short).
@@ -109,6 +124,75 @@ SBG_GEOM_FN u64 scan5_wide_valid(const Scan5WideTask& t, int lo, int hi,
     }
   }
   return valid;
+}
+
+// ---------------------------------------------------------------------------
+// Chunks of k_scan5_wave's triple queue. A wave takes a whole chunk of
+// consecutive triples with one atomic on a chunk counter; chunk k of a queue
+// of `units` triples that `waves` waves share is [first, first + count),
+// relative to the queue's first triple. The bulk comes in chunks of `size`
+// triples: at most SCAN5_CHUNK_MAX (one triple per lane of the wave that
+// decodes the chunk), few enough that every wave still gets
+// SCAN5_CHUNKS_PER_WAVE of them, and at least SCAN5_CHUNK_MIN, because one
+// address serves only about one agent-scope atomic per 12 ns: a scan with
+// few triples must not pay one per triple (the host sizes its grid to a
+// chunk of SCAN5_CHUNK_MIN per wave). The end of the queue is handed out in
+// `waves` chunks of each smaller size size / 2, size / 4, ..., down to
+// SCAN5_CHUNK_MIN, so the waves finish close together.
+// ---------------------------------------------------------------------------
+constexpr int SCAN5_CHUNK_MAX = 64;
+constexpr int SCAN5_CHUNK_MIN = 8;
+constexpr int SCAN5_CHUNKS_PER_WAVE = 8;
+
+SBG_GEOM_FN int scan5_chunk_size(i64 units, int waves) {
+  const i64 s = units / (static_cast<i64>(SCAN5_CHUNKS_PER_WAVE) * waves);
+  return s < SCAN5_CHUNK_MIN
+             ? SCAN5_CHUNK_MIN
+             : (s > SCAN5_CHUNK_MAX ? SCAN5_CHUNK_MAX : static_cast<int>(s));
+}
+
+// What does not depend on k, worked out once per wave (the divisions).
+struct Scan5ChunkPlan {
+  i64 units;
+  int waves;
+  int size;   // triples per bulk chunk
+  i64 bulk;   // triples handed out in bulk chunks
+  i64 nbulk;  // bulk chunks; the last one may be short
+};
+
+SBG_GEOM_FN Scan5ChunkPlan scan5_chunk_plan(i64 units, int waves) {
+  Scan5ChunkPlan p;
+  p.units = units < 0 ? 0 : units;
+  p.waves = waves;
+  p.size = scan5_chunk_size(p.units, waves);
+  i64 tail = 0;  // size > CHUNK_MIN implies units >= 8 waves size > tail
+  for (int s = p.size / 2; s >= SCAN5_CHUNK_MIN; s /= 2) {
+    tail += static_cast<i64>(waves) * s;
+  }
+  p.bulk = p.units - tail;
+  p.nbulk = (p.bulk + p.size - 1) / p.size;
+  return p;
+}
+
+struct Scan5Chunk {
+  i64 first;
+  int count;  // 0: k is past the last chunk
+};
+
+SBG_GEOM_FN Scan5Chunk scan5_chunk(const Scan5ChunkPlan& p, i64 k) {
+  if (k < p.nbulk) {
+    const i64 first = k * p.size;
+    const i64 left = p.bulk - first;
+    return {first, left < p.size ? static_cast<int>(left) : p.size};
+  }
+  k -= p.nbulk;
+  i64 first = p.bulk;
+  for (int s = p.size / 2; s >= SCAN5_CHUNK_MIN; s /= 2) {
+    if (k < p.waves) return {first + k * s, s};
+    k -= p.waves;
+    first += static_cast<i64>(p.waves) * s;
+  }
+  return {p.units, 0};
 }
 
 }  // namespace sbg

@@ -9,6 +9,8 @@ namespace sbg {
 
 bool gpu_available() { return false; }
 int gpu_count() { return 0; }
+int scan5_wave_min_pool() { return SCAN5_WAVE_MIN_POOL; }
+void set_scan5_wave_min_pool(int) {}
 
 std::unique_ptr<GpuEngine> GpuEngine::create(int, std::string* err) {
   if (err != nullptr) *err = "sanitizer build: GPU engine stubbed out";

@@ -21,6 +21,7 @@
 #include "sbg/rng.hpp"
 #include "sbg/sboxio.hpp"
 #include "sbg/scan.hpp"
+#include "sbg/scan5_cell.hpp"
 #include "sbg/scan5_geom.hpp"
 #include "sbg/search.hpp"
 #include "sbg/state.hpp"
@@ -104,6 +105,14 @@ void grow_pool_random(state& st, int target_gates, u64 seed) {
     // Avoid duplicate truth tables (degenerate pools slow nothing but add
     // trivial hits): keep anyway — the reference pool also contains
     // near-duplicates; uniqueness is not required.
+  }
+}
+
+// A table as the eight dwords of sbg/scan5_cell.hpp.
+void tt_dwords(const ttable& t, u32 (&d)[8]) {
+  for (int w = 0; w < 4; w++) {
+    d[2 * w] = static_cast<u32>(t.w[w]);
+    d[2 * w + 1] = static_cast<u32>(t.w[w] >> 32);
   }
 }
 
@@ -230,6 +239,46 @@ PYBIND11_MODULE(_core, m) {
     }
     return out;
   }, py::arg("units"), py::arg("waves"));
+
+  // --- k_scan5_wave's per-triple set-up (sbg/scan5_cell.hpp, shared with
+  // the kernel): prefix-cell sizes, live cells, screen cell, list heads ---
+  // (live mask, screen cell u0, sizes of u0's target-1 and target-0 sides)
+  // of the triple with tables ta, tb, tc.
+  m.def("scan5_screen_cell", [](py::bytes ta, py::bytes tb, py::bytes tc,
+                                py::bytes T1, py::bytes T0) {
+    u32 d[5][8];
+    const py::bytes* in[5] = {&ta, &tb, &tc, &T1, &T0};
+    for (int i = 0; i < 5; i++) tt_dwords(tt_from_bytes(*in[i]), d[i]);
+    const Scan5ScreenCell s = scan5_screen_cell(d[0], d[1], d[2], d[3], d[4]);
+    return py::make_tuple(s.live, s.u0, s.c1, s.c0);
+  }, py::arg("ta"), py::arg("tb"), py::arg("tc"), py::arg("T1"),
+     py::arg("T0"));
+  // The positions of prefix cell u of the triple, as a 256-bit table.
+  m.def("scan5_cell", [](py::bytes ta, py::bytes tb, py::bytes tc, int u) {
+    if (u < 0 || u > 7) throw std::invalid_argument("scan5_cell: 0 <= u <= 7");
+    u32 a[8], b[8], c[8];
+    tt_dwords(tt_from_bytes(ta), a);
+    tt_dwords(tt_from_bytes(tb), b);
+    tt_dwords(tt_from_bytes(tc), c);
+    ttable out = tt_zero_table();
+    for (int w = 0; w < 8; w++) {
+      out.w[w >> 1] |= static_cast<u64>(scan5_cell_dword(a[w], b[w], c[w], u))
+                       << (32 * (w & 1));
+    }
+    return tt_to_bytes(out);
+  });
+  // The first SCAN5_HEAD_BYTES positions of a side, padded with the last.
+  m.attr("SCAN5_HEAD_BYTES") = SCAN5_HEAD_BYTES;
+  m.def("scan5_side_head", [](py::bytes side) {
+    u32 h[8], head[4];
+    tt_dwords(tt_from_bytes(side), h);
+    scan5_side_head(h, head);
+    std::vector<int> out;
+    for (int i = 0; i < SCAN5_HEAD_BYTES; i++) {
+      out.push_back(static_cast<int>((head[i >> 2] >> (8 * (i & 3))) & 0xffu));
+    }
+    return out;
+  });
 
   // --- lutcover primitives (for oracle tests) ---
   m.def("naive_check_n_lut_possible",

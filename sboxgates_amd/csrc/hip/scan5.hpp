@@ -5,6 +5,7 @@
 // (scan_launch.hpp).
 #pragma once
 
+#include "sbg/scan5_cell.hpp"
 #include "sbg/scan5_geom.hpp"
 #include "scan_device.hpp"
 
@@ -234,14 +235,21 @@ __device__ __forceinline__ void gt_accumulate_step(GtSide<NW>& s, u32 pw,
 // vector work. head1, head0: the lists' first GT_HEAD_BYTES, already in
 // scalars (gt_build_lists' `head`), so that the first G reads wait for no
 // list read. Call from code that the whole wave runs together.
-template <int NW>
+// past_heads() runs before every read of list1 / list0, which happens only
+// when a side is longer than its head and the walk gets that far: a caller
+// that builds the lists on demand does it there.
+struct GtListsReady {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int NW, class PastHeads = GtListsReady>
 __device__ __forceinline__ GtWords<NW> gt_screen(const u32 (&head1)[4],
                                                  const u32 (&head0)[4],
                                                  const u8* list1, int n1,
                                                  const u8* list0, int n0,
                                                  const u32* gw, const u32* gx,
                                                  u32 xbit,
-                                                 const GtWords<NW>& valid) {
+                                                 const GtWords<NW>& valid,
+                                                 PastHeads past_heads = {}) {
   static_assert(GT_LIST_STEP == 4);  // one dword of list bytes per step
   static_assert(GT_HEAD_BYTES == 16);  // one pass of the loop below
   GtWords<NW> pend = valid;
@@ -267,6 +275,7 @@ __device__ __forceinline__ GtWords<NW> gt_screen(const u32 (&head1)[4],
         pw0[j] = head0[j];
       }
     } else {
+      past_heads();
       if (k < n1) {
         const lds_u32x4 v = *reinterpret_cast<const lds_u32x4*>(list1 + k);
         pw1[0] = __builtin_amdgcn_readfirstlane(v.x);
@@ -827,11 +836,13 @@ __global__ void __launch_bounds__(SCAN_BLOCK, 4) k_scan5(ScanArgs args) {
 // gt_build_lists by one whole wave, both sides at once, lane = 32 side +
 // part: each lane files the 8
 // positions of byte `part` of its side of the cell's forced sets (h1, h0: 4
-// words each, disjoint). Returns the lists' padded lengths and the target-0
-// list's byte offset, 10 bits each, the same in every lane.
-__device__ __forceinline__ u32 gt_build_lists_wave(const u64* h1,
-                                                   const u64* h0, u8* list,
-                                                   u8* head, int lane) {
+// words each, disjoint). No heads: k_scan5_wave has them in registers
+// (scan5_side_head). The lists' padded lengths are those of gt_build_lists:
+// the side's size rounded up to GT_LIST_STEP, the target-0 list at the next
+// multiple of 16 behind the target-1 list.
+__device__ __forceinline__ void gt_build_lists_wave(const u64* h1,
+                                                    const u64* h0, u8* list,
+                                                    int lane) {
   const int side = lane >> 5, part = lane & 31;
   const int wd = part >> 3, sh = (part & 7) * 8;
   const u64* h = side == 0 ? h1 : h0;
@@ -854,25 +865,12 @@ __device__ __forceinline__ u32 gt_build_lists_wave(const u64* h1,
     int p = 0;
     for (; mine != 0; mine &= mine - 1) {
       p = part * 8 + __ffs(mine) - 1;
-      if (at < GT_HEAD_BYTES) {
-        head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
-      }
       list[base + at++] = static_cast<u8>(p);
     }
     if (at == total) {  // the side's last position is here: pad with it
-      for (; at < padded; at++) {
-        if (at < GT_HEAD_BYTES) {
-          head[side * GT_HEAD_BYTES + at] = static_cast<u8>(p);
-        }
-        list[base + at] = static_cast<u8>(p);
-      }
+      for (; at < padded; at++) list[base + at] = static_cast<u8>(p);
     }
   }
-  const u32 n1 =
-      static_cast<u32>((total1 + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1));
-  const u32 n0 =
-      static_cast<u32>((total0 + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1));
-  return n1 | (n0 << 10) | (static_cast<u32>(off0) << 20);
 }
 
 
@@ -880,140 +878,241 @@ __device__ __forceinline__ u32 gt_build_lists_wave(const u64* h1,
 // k_scan5_wave: a wave owns its triples. The block stages the pool and
 // builds G once; from then on its waves run on their own and meet again
 // only to add up `evaluated`. A wave takes a chunk of consecutive triples
-// off the queue with one atomic (sbg/scan5_geom.hpp has the chunk rule),
-// decodes them one per lane, and for every live triple builds the prefix
-// cells, picks the screen cell, lists its positions and walks the
-// triple's tasks, all in a slice of LDS that only this wave touches. What
-// the walk needs of the triple stays in scalars for the whole triple.
+// off the queue with one atomic (sbg/scan5_geom.hpp has the chunk rule) and
+// sets them all up at once, one triple per lane (sbg/scan5_cell.hpp): the
+// triple's ids and pair window, the sizes of its eight prefix cells, the
+// live cells, the screen cell and the first GT_HEAD_BYTES positions of the
+// screen cell's two sides. The walk (scan5_wave_walk, one call per chunk)
+// takes a triple's values out of its lane with v_readlane and keeps them in
+// scalars for the whole triple. What only the rare path reads (all eight
+// prefix cells, the prefix's gate ids) and what only a long screen reads
+// (the complete position lists) is built by the whole wave the first time
+// a triple needs it, in a slice of LDS that only this wave touches.
 // ---------------------------------------------------------------------------
 
-// A wave's private LDS: the current triple's prefix cells (the rare path
-// reads them), the screen cell's position lists and their heads, and the
-// prefix's gate ids for the survivor routine.
+// A wave's private LDS, filled on demand for the triple it is walking: the
+// prefix cells and the prefix's gate ids (for the rare path) and the screen
+// cell's position lists (for a screen that goes past the heads).
 struct alignas(16) Scan5WaveSlice {
   u64 H1[8][4];
   u64 H0[8][4];
   u8 pos[GT_LIST_BYTES];
-  u32 head[2 * GT_HEAD_BYTES / 4];
   u16 abc[8];  // 3 used
 };
 
-typedef __attribute__((address_space(3))) const Scan5WaveSlice lds_cslice;
+typedef __attribute__((address_space(3))) Scan5WaveSlice lds_slice;
 
-// Set in scan5_wave_walk's result: the scan was aborted, the wave stops.
-constexpr u64 SCAN5_WALK_ABORTED = 1ULL << 63;
+// Set in scan5_wave_walk's result: the wave's scan ends here (aborted, or
+// ordered and past the best hit known).
+constexpr u64 SCAN5_WALK_STOP = 1ULL << 63;
 
-// Walk of one triple by one wave: returns the pairs this lane evaluated.
-// The triple's values arrive as the same number in every lane and go
-// through scalars here: its last gate c, its pair window [lo, hi), its flat
-// rank base, the position lists' padded lengths and the target-0 list's
-// offset (10 bits each in `lens`), the live cells and the screen cell << 8
-// (`cells`). Not inlined: inside the kernel this loop's invariants were
-// spilled and reloaded from scratch in every step; as a function it gets
-// registers of its own.
+// The rare path of a step: the pairs `pend` of row d that passed the screen
+// (bit i: the pair (d, e0 + i) of flat rank rank0 + i) go through the other
+// live cells and the solver. Not inlined, to keep its registers out of the
+// walk's.
+template <int STR, bool ORD>
+__device__ __attribute__((noinline)) void scan5_wave_rare(
+    const ScanArgs& args, DevCtl* ctl, lds_cu64* l_pool, lds_slice* l_slice,
+    u32 other_live, i64 rank0, int d, int e0, u64 pend) {
+  const u64* s_pool = (const u64*)l_pool;
+  const Scan5WaveSlice* sl = (const Scan5WaveSlice*)l_slice;
+  while (pend != 0) {
+    const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
+    pend &= pend - 1;
+    scan5_after_screen<STR, ORD>(args, ctl, s_pool, sl->H1, sl->H0, sl->abc,
+                                 other_live, rank0 + i, d, e0 + i);
+  }
+}
+
+// What the chunk set-up leaves for the walk in lane i about triple i. Packed
+// `cells`: live cells | screen cell << 8 | size of its target-1 side << 12 |
+// size of its target-0 side << 21 (sizes are at most 256).
+static_assert(GT_HEAD_BYTES == SCAN5_HEAD_BYTES);
+struct Scan5WaveTriple {
+  int ab, c, lo, hi, base_lo, base_hi, cells;
+  u32 head1[4], head0[4];
+};
+
+// Walk of one chunk's live triples (`todo`: their lanes) by one wave:
+// returns the pairs this lane evaluated, with SCAN5_WALK_STOP if the wave's
+// scan ends. Every argument but `todo` and the LDS arrays is per lane (v.*
+// of lane i describe triple i); a triple's values go through v_readlane
+// into scalars. Not inlined: inside the kernel the step loop's invariants
+// were spilled and reloaded from scratch in every step; as a function it
+// gets registers of its own.
 template <int STR, bool ORD>
 __device__ __attribute__((noinline)) u64 scan5_wave_walk(
     const ScanArgs& args, DevCtl* ctl, int pad, lds_cu64* l_pool,
-    lds_cu32* l_G, lds_cslice* l_slice, int c_, int lo_, int hi_, i64 base_,
-    u32 lens_, u32 cells_) {
+    lds_cu32* l_G, lds_cu32* l_T, lds_slice* l_slice, u64 todo_, int v_ab,
+    int v_c, int v_lo, int v_hi, int v_base_lo, int v_base_hi, int v_cells,
+    u32 v_h10, u32 v_h11, u32 v_h12, u32 v_h13, u32 v_h00, u32 v_h01,
+    u32 v_h02, u32 v_h03) {
   constexpr int NW = SCAN5_WIDE_WORDS;
   constexpr int GB = SCAN5_WIDE_GB;
   static_assert(GB == 64);  // a lane a row
   const u64* s_pool = (const u64*)l_pool;
   const u32* s_G = (const u32*)l_G;
-  const Scan5WaveSlice* sl = (const Scan5WaveSlice*)l_slice;
+  Scan5WaveSlice* sl = (Scan5WaveSlice*)l_slice;
   const int lane = threadIdx.x & 63;
-  const int n = args.n;
-  const int count_all = args.count_all;
-  const u64 excl = args.excl;
-  const int c = static_cast<int>(dev_uniform(c_));
-  const int lo = static_cast<int>(dev_uniform(lo_));
-  const int hi = static_cast<int>(dev_uniform(hi_));
-  const i64 base = static_cast<i64>(
-      static_cast<u64>(dev_uniform(static_cast<u32>(base_))) |
-      static_cast<u64>(dev_uniform(static_cast<u32>(base_ >> 32))) << 32);
-  const u32 lens = dev_uniform(lens_), cells = dev_uniform(cells_);
-  const int n1 = static_cast<int>(lens & 0x3ffu);
-  const int n0 = static_cast<int>((lens >> 10) & 0x3ffu);
-  const u8* list0 = sl->pos + (lens >> 20);
-  const u32 live = cells & 0xffu;
-  const int u0 = static_cast<int>(cells >> 8);
+  // Through scalars, so that the per-lane arguments get the registers.
+  pad = static_cast<int>(dev_uniform(static_cast<u32>(pad)));
+  const int n = static_cast<int>(dev_uniform(static_cast<u32>(args.n)));
+  const int count_all =
+      static_cast<int>(dev_uniform(static_cast<u32>(args.count_all)));
+  const u64 excl = dev_uniform64(args.excl);
   u64 local_eval = 0;
-  const lds_u32x4 rh1 = *reinterpret_cast<const lds_u32x4*>(&sl->head[0]);
-  const lds_u32x4 rh0 = *reinterpret_cast<const lds_u32x4*>(
-      &sl->head[GT_HEAD_BYTES / 4]);
-  const u32 head1[4] = {dev_uniform(rh1.x), dev_uniform(rh1.y),
-                        dev_uniform(rh1.z), dev_uniform(rh1.w)};
-  const u32 head0[4] = {dev_uniform(rh0.x), dev_uniform(rh0.y),
-                        dev_uniform(rh0.z), dev_uniform(rh0.w)};
+  u64 todo = dev_uniform64(todo_);
 
-  // Walk. A task is (row d, word group): the pairs (d, e) with e among
-  // the GB gates of G's words [NW wg, NW wg + NW). The tasks run through
-  // the groups from the last one down, consecutive rows on consecutive
-  // lanes, 64 tasks a step: (wg, row0) is the step's first task, and a
-  // lane whose row lies past the group's end is in the next group down
-  // (which has 64 rows fewer, or is the triple's last).
-  const Scan5WideGroups g = scan5_wide_groups(n, pad, c);
-  int wg = g.w_max, rows = n - 2 - c, row0 = 0;
-  while (wg >= g.w_min) {
-    // Unordered first-hit scans poll once per step, as often per pair
-    // walked as the tasks of the batch walk did.
-    if (!ORD && !count_all && wave_abort(ctl)) {
-      return local_eval | SCAN5_WALK_ABORTED;
+  for (; todo != 0; todo &= todo - 1) {
+    const int j = __ffsll(static_cast<unsigned long long>(todo)) - 1;
+    const int ab = wave_lane_value(v_ab, j);
+    const int a = ab & 0xffff, b = ab >> 16;
+    const int c = wave_lane_value(v_c, j);
+    const int lo = wave_lane_value(v_lo, j);
+    const int hi = wave_lane_value(v_hi, j);
+    const i64 base = static_cast<i64>(
+        static_cast<u64>(static_cast<u32>(wave_lane_value(v_base_lo, j))) |
+        static_cast<u64>(static_cast<u32>(wave_lane_value(v_base_hi, j)))
+            << 32);
+    // Ordered: ranks rise with the triple index, so a triple that begins
+    // above the best hit known ends this wave's scan. A triple it has
+    // begun runs to its end.
+    if constexpr (ORD) {
+      if (!count_all && static_cast<u64>(base) > wave_best(ctl)) {
+        return local_eval | SCAN5_WALK_STOP;
+      }
     }
-    const int rows_down = scan5_wide_rows(pad, c, wg - 1);
-    int d2 = row0 + lane, lwg = wg;
-    bool mine = true;
-    if (d2 >= rows) {
-      d2 -= rows;
-      lwg = wg - 1;
-      mine = lwg >= g.w_min && d2 < rows_down;
-    }
-    if (!mine) {  // no task: any address inside G will do
-      d2 = 0;
-      lwg = wg;
-    }
-    // Bit i of the task is the pair (d, e0 + i), flat index q0 + i;
-    // valid: clipped to e > d and to the triple's [lo, hi) window,
-    // without the excluded gates.
-    const Scan5WideTask wt = scan5_wide_task_at(n, pad, c, lwg, d2);
-    const u64 valid = mine ? scan5_wide_valid(wt, lo, hi, excl) : 0;
-    row0 += 64;
-    while (wg >= g.w_min && row0 >= rows) {
-      row0 -= rows;
-      wg--;
-      rows = scan5_wide_rows(pad, c, wg);
-    }
-    if (!__any(valid != 0)) continue;
-    local_eval += __popcll(valid);
+    const u32 cells = static_cast<u32>(wave_lane_value(v_cells, j));
+    const u32 live = cells & 0xffu;
+    const int u0 = static_cast<int>((cells >> 8) & 7u);
+    const int c1 = static_cast<int>((cells >> 12) & 0x1ffu);
+    const int c0 = static_cast<int>(cells >> 21);
+    const int n1 = (c1 + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1);
+    const int n0 = (c0 + GT_LIST_STEP - 1) & ~(GT_LIST_STEP - 1);
+    const u8* list0 = sl->pos + ((c1 + 15) & ~15);
+    const u32 head1[4] = {
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h10), j)),
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h11), j)),
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h12), j)),
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h13), j))};
+    const u32 head0[4] = {
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h00), j)),
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h01), j)),
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h02), j)),
+        static_cast<u32>(wave_lane_value(static_cast<int>(v_h03), j))};
 
-    // Screen: the listed positions of the screen cell. Per position the
-    // lanes read G at their candidate words (the same address across
-    // most of a wave: LDS broadcast) and at d's own word for td's bit.
-    GtWords<NW> vw;
+    // On demand, by the whole wave, at most once per triple. The syncs on
+    // either side order the build against the reads of the triple before
+    // and against its own readers.
+    bool cells_built = false, lists_built = false;
+    // The eight prefix cells, masked with target-1 / target-0, and the
+    // prefix's ids: lane = (cell u = lane & 7, dword = lane >> 3).
+    const auto need_cells = [&]() {
+      if (cells_built) return;
+      cells_built = true;
+      wave_lds_sync();
+      const int cu = lane & 7, cdw = lane >> 3;
+      const lds_u32* pool32 = reinterpret_cast<const lds_u32*>(s_pool);
+      const u32 cell = scan5_cell_dword(pool32[a * (2 * STR) + cdw],
+                                        pool32[b * (2 * STR) + cdw],
+                                        pool32[c * (2 * STR) + cdw], cu);
+      reinterpret_cast<lds_u32*>(&sl->H1[0][0])[cu * 8 + cdw] =
+          cell & l_T[cdw];
+      reinterpret_cast<lds_u32*>(&sl->H0[0][0])[cu * 8 + cdw] =
+          cell & l_T[8 + cdw];
+      if (lane == 0) {
+        sl->abc[0] = static_cast<u16>(a);
+        sl->abc[1] = static_cast<u16>(b);
+        sl->abc[2] = static_cast<u16>(c);
+      }
+      wave_lds_sync();
+    };
+    // The screen cell's complete position lists.
+    const auto need_lists = [&]() {
+      if (lists_built) return;
+      lists_built = true;
+      need_cells();
+      gt_build_lists_wave(sl->H1[u0], sl->H0[u0], sl->pos, lane);
+      wave_lds_sync();
+    };
+
+    // Walk. A task is (row d, word group): the pairs (d, e) with e among
+    // the GB gates of G's words [NW wg, NW wg + NW). The tasks run through
+    // the groups from the last one down, consecutive rows on consecutive
+    // lanes, 64 tasks a step: (wg, row0) is the step's first task, and a
+    // lane whose row lies past the group's end is in the next group down
+    // (which has 64 rows fewer, or is the triple's last).
+    const Scan5WideGroups g = scan5_wide_groups(n, pad, c);
+    int wg = g.w_max, rows = n - 2 - c, row0 = 0;
+    while (wg >= g.w_min) {
+      // Unordered first-hit scans poll once per step, as often per pair
+      // walked as the tasks of the batch walk did.
+      if (!ORD && !count_all && wave_abort(ctl)) {
+        return local_eval | SCAN5_WALK_STOP;
+      }
+      const int rows_down = scan5_wide_rows(pad, c, wg - 1);
+      int d2 = row0 + lane, lwg = wg;
+      bool mine = true;
+      if (d2 >= rows) {
+        d2 -= rows;
+        lwg = wg - 1;
+        mine = lwg >= g.w_min && d2 < rows_down;
+      }
+      if (!mine) {  // no task: any address inside G will do
+        d2 = 0;
+        lwg = wg;
+      }
+      // Bit i of the task is the pair (d, e0 + i), flat index q0 + i;
+      // valid: clipped to e > d and to the triple's [lo, hi) window,
+      // without the excluded gates.
+      const Scan5WideTask wt = scan5_wide_task_at(n, pad, c, lwg, d2);
+      const u64 valid = mine ? scan5_wide_valid(wt, lo, hi, excl) : 0;
+      row0 += 64;
+      while (wg >= g.w_min && row0 >= rows) {
+        row0 -= rows;
+        wg--;
+        rows = scan5_wide_rows(pad, c, wg);
+      }
+      if (!__any(valid != 0)) continue;
+      local_eval += __popcll(valid);
+
+      // Screen: the listed positions of the screen cell. Per position the
+      // lanes read G at their candidate words (the same address across
+      // most of a wave: LDS broadcast) and at d's own word for td's bit.
+      GtWords<NW> vw;
 #pragma unroll
-    for (int w = 0; w < NW; w++) {
-      vw.w[w] = static_cast<u32>(valid >> (32 * w));
-    }
-    const GtWords<NW> pw = gt_screen<NW>(
-        head1, head0, sl->pos, n1, list0, n0, &s_G[NW * wt.wg],
-        &s_G[(wt.d + pad) >> 5], (wt.d + pad) & 31, vw);
-    u64 pend = 0;
+      for (int w = 0; w < NW; w++) {
+        vw.w[w] = static_cast<u32>(valid >> (32 * w));
+      }
+      const GtWords<NW> pw = gt_screen<NW>(
+          head1, head0, sl->pos, n1, list0, n0, &s_G[NW * wt.wg],
+          &s_G[(wt.d + pad) >> 5], (wt.d + pad) & 31, vw, need_lists);
+      u64 pend = 0;
 #pragma unroll
-    for (int w = 0; w < NW; w++) {
-      pend |= static_cast<u64>(pw.w[w]) << (32 * w);
-    }
+      for (int w = 0; w < NW; w++) {
+        pend |= static_cast<u64>(pw.w[w]) << (32 * w);
+      }
 
-    // Rare path. The screen only ever passes too much.
-    while (pend != 0) {
-      const int i = __ffsll(static_cast<unsigned long long>(pend)) - 1;
-      pend &= pend - 1;
-      scan5_after_screen<STR, ORD>(args, ctl, s_pool, sl->H1, sl->H0,
-                                   sl->abc, live & ~(1u << u0),
-                                   base + wt.q0 + i, wt.d, wt.e0 + i);
+      // Rare path. The screen only ever passes too much.
+      if (!__any(pend != 0)) continue;
+      need_cells();
+      scan5_wave_rare<STR, ORD>(args, ctl, l_pool, l_slice,
+                                live & ~(1u << u0), base + wt.q0, wt.d, wt.e0,
+                                pend);
     }
   }
   return local_eval;
+}
+
+// Eight dwords of a pool row, two 16-byte LDS reads (rows are 32 B apart).
+template <int STR>
+__device__ __forceinline__ void scan5_load_row(const u64* s_pool, int id,
+                                               u32 (&r)[8]) {
+  static_assert(STR == PSTR_DENSE);
+  const lds_u32x4* q = reinterpret_cast<const lds_u32x4*>(&s_pool[id * STR]);
+  const lds_u32x4 x = q[0], y = q[1];
+  r[0] = x.x; r[1] = x.y; r[2] = x.z; r[3] = x.w;
+  r[4] = y.x; r[5] = y.y; r[6] = y.z; r[7] = y.w;
 }
 
 // q_begin, q_units: the first triple of the queue and the number of triples
@@ -1026,7 +1125,10 @@ __device__ __forceinline__ void scan5_wave_scan(const ScanArgs& args,
   __shared__ alignas(16) u64 s_pool[MAX_GATES * STR];
   __shared__ alignas(16) u32 s_G[GT_DWORDS];
   __shared__ Scan5WaveSlice s_slice[SCAN_BLOCK / 64];
-  __shared__ u64 s_T[2][4];  // T1, T0: lanes index them by their own dword
+  // T1 and T0 for the on-demand cell build, which reads them as 16 dwords
+  // indexed by lane: dword w of T1 at [w], of T0 at [8 + w] (dword 2 k is
+  // the low half of word k).
+  __shared__ u64 s_T[2][4];
 
   const int n = args.n;
   const int pad = scan5_wide_pad(n);  // shift of the gate ids inside G
@@ -1048,15 +1150,17 @@ __device__ __forceinline__ void scan5_wave_scan(const ScanArgs& args,
   const i64 total3 = cf3(n);
   const Scan5ChunkPlan plan = scan5_chunk_plan(
       q_units, static_cast<int>(gridDim.x) * (SCAN_BLOCK / 64));
-  // Cell build: lane = (cell u, dword dw) of the 8 cells x 8 dwords a side;
-  // cells on the low lane bits, so that lanes 0..7 speak for the 8 cells.
-  const int cu = lane & 7, cdw = lane >> 3;
-  const lds_u32* pool32 = reinterpret_cast<const lds_u32*>(s_pool);
-  const u32 T1d = reinterpret_cast<const lds_u32*>(s_T[0])[cdw];
-  const u32 T0d = reinterpret_cast<const lds_u32*>(s_T[1])[cdw];
+  u32 T1[8], T0[8];  // wave-uniform: kernel arguments
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    T1[2 * w] = static_cast<u32>(args.T1.w[w]);
+    T1[2 * w + 1] = static_cast<u32>(args.T1.w[w] >> 32);
+    T0[2 * w] = static_cast<u32>(args.T0.w[w]);
+    T0[2 * w + 1] = static_cast<u32>(args.T0.w[w] >> 32);
+  }
   u64 local_eval = 0;
 
-  for (bool done = false; !done;) {
+  for (;;) {
     // Dequeue: one lane, one atomic per chunk. Ordered: a known hit takes
     // the abort flag's place; chunks come in increasing triple order, so
     // every chunk not yet taken ranks above any hit already known.
@@ -1078,95 +1182,49 @@ __device__ __forceinline__ void scan5_wave_scan(const ScanArgs& args,
     const Scan5Chunk ch = scan5_chunk(plan, k);
     if (ch.count == 0) break;
 
-    // Lane i decodes triple i of the chunk and clips its pair window.
+    // Lane i sets up triple i of the chunk: ids and pair window, then, if
+    // the window is not empty, the cell sizes, the live cells, the screen
+    // cell and the heads of its two position lists.
     PrefixWindow<3> p;
     if (lane < ch.count) {
       p = decode_prefix_window<3>(q_begin + ch.first + lane, total3, args);
       drop_dead_prefix(p, args);
     }
-    const int v_ab = p.ids[0] | (p.ids[1] << 16);
-    const int v_c = p.ids[2];
-    const int v_lo = static_cast<int>(p.lo);  // <= C(m, 2) < 2^17
-    const int v_hi = static_cast<int>(p.hi);
-    const int v_base_lo = static_cast<int>(p.base);
-    const int v_base_hi = static_cast<int>(p.base >> 32);
-
-    for (u64 todo = __ballot(p.lo < p.hi); todo != 0 && !done;
-         todo &= todo - 1) {
-      const int j = __ffsll(static_cast<unsigned long long>(todo)) - 1;
-      const int ab = wave_lane_value(v_ab, j);
-      const int a = ab & 0xffff, b = ab >> 16;
-      const int c = wave_lane_value(v_c, j);
-      const int lo = wave_lane_value(v_lo, j);
-      const int hi = wave_lane_value(v_hi, j);
-      const i64 base = static_cast<i64>(
-          static_cast<u64>(static_cast<u32>(wave_lane_value(v_base_lo, j))) |
-          static_cast<u64>(static_cast<u32>(wave_lane_value(v_base_hi, j)))
-              << 32);
-      // Ordered: ranks rise with the triple index, so a triple that begins
-      // above the best hit known ends this wave's scan. A triple it has
-      // begun runs to its end.
-      if constexpr (ORD) {
-        if (!count_all && static_cast<u64>(base) > wave_best(ctl)) {
-          done = true;
-          break;
-        }
+    const bool alive = p.lo < p.hi;
+    Scan5WaveTriple v = {};
+    v.ab = p.ids[0] | (p.ids[1] << 16);
+    v.c = p.ids[2];
+    v.lo = static_cast<int>(p.lo);  // <= C(m, 2) < 2^17
+    v.hi = static_cast<int>(p.hi);
+    v.base_lo = static_cast<int>(p.base);
+    v.base_hi = static_cast<int>(p.base >> 32);
+    if (alive) {
+      u32 ra[8], rb[8], rc[8], s1[8], s0[8];
+      scan5_load_row<STR>(s_pool, p.ids[0], ra);
+      scan5_load_row<STR>(s_pool, p.ids[1], rb);
+      scan5_load_row<STR>(s_pool, p.ids[2], rc);
+      const Scan5ScreenCell sc = scan5_screen_cell(ra, rb, rc, T1, T0);
+#pragma unroll
+      for (int w = 0; w < 8; w++) {
+        const u32 cell = scan5_cell_dword(ra[w], rb[w], rc[w], sc.u0);
+        s1[w] = cell & T1[w];
+        s0[w] = cell & T0[w];
       }
-
-      // The eight prefix cells, masked with target-1 / target-0.
-      u32 cell = ~0u;
-      {
-        const u32 ra = pool32[a * (2 * STR) + cdw];
-        const u32 rb = pool32[b * (2 * STR) + cdw];
-        const u32 rc = pool32[c * (2 * STR) + cdw];
-        cell &= (cu & 4) ? ra : ~ra;
-        cell &= (cu & 2) ? rb : ~rb;
-        cell &= (cu & 1) ? rc : ~rc;
-      }
-      const u32 h1 = cell & T1d, h0 = cell & T0d;
-      reinterpret_cast<lds_u32*>(&sl->H1[0][0])[cu * 8 + cdw] = h1;
-      reinterpret_cast<lds_u32*>(&sl->H0[0][0])[cu * 8 + cdw] = h0;
-      if (lane == 0) {
-        sl->abc[0] = static_cast<u16>(a);
-        sl->abc[1] = static_cast<u16>(b);
-        sl->abc[2] = static_cast<u16>(c);
-      }
-      // Sizes of the cell's two sides (at most 256 each), summed over its
-      // dwords. A cell with an empty side cannot contradict: only the
-      // others are live. The screen runs on the live cell whose smaller
-      // side is largest, ties to the lower cell (on the benchmark pool the
-      // lowest live cell lets ~1.6% of candidates through, this one ~none);
-      // cell 7 when none is live.
-      u32 sizes = static_cast<u32>(__popc(h1)) |
-                  (static_cast<u32>(__popc(h0)) << 16);
-      sizes += __shfl_xor(sizes, 8);
-      sizes += __shfl_xor(sizes, 16);
-      sizes += __shfl_xor(sizes, 32);
-      const u32 c1 = sizes & 0xffffu, c0 = sizes >> 16;
-      const bool cell_live = c1 != 0 && c0 != 0;
-      const u32 live = static_cast<u32>(__ballot(cell_live)) & 0xffu;
-      u32 key = cell_live
-                    ? ((c1 < c0 ? c1 : c0) << 3) | static_cast<u32>(7 - cu)
-                    : 0u;
-      key = max(key, static_cast<u32>(__shfl_xor(key, 1)));
-      key = max(key, static_cast<u32>(__shfl_xor(key, 2)));
-      key = max(key, static_cast<u32>(__shfl_xor(key, 4)));
-      const int u0 = 7 - static_cast<int>(dev_uniform(key) & 7u);
-      wave_lds_sync();
-
-      // The screen cell's position lists and their heads.
-      const u32 lens = dev_uniform(gt_build_lists_wave(
-          sl->H1[u0], sl->H0[u0], sl->pos, reinterpret_cast<u8*>(sl->head),
-          lane));
-      wave_lds_sync();
-      const u64 r = scan5_wave_walk<STR, ORD>(
-          args, ctl, pad, (lds_cu64*)s_pool, (lds_cu32*)s_G, (lds_cslice*)sl,
-          c, lo, hi, base, lens, live | (static_cast<u32>(u0) << 8));
-      local_eval += r & ~SCAN5_WALK_ABORTED;
-      done = (r & SCAN5_WALK_ABORTED) != 0;
-      // The next triple overwrites the slice.
-      wave_lds_sync();
+      scan5_side_head(s1, v.head1);
+      scan5_side_head(s0, v.head0);
+      v.cells = static_cast<int>(sc.live | (static_cast<u32>(sc.u0) << 8) |
+                                 (static_cast<u32>(sc.c1) << 12) |
+                                 (static_cast<u32>(sc.c0) << 21));
     }
+    const u64 todo = __ballot(alive);
+    if (todo == 0) continue;
+    const u64 r = scan5_wave_walk<STR, ORD>(
+        args, ctl, pad, (lds_cu64*)s_pool, (lds_cu32*)s_G, (lds_cu32*)s_T,
+        (lds_slice*)sl, todo, v.ab, v.c, v.lo, v.hi, v.base_lo, v.base_hi,
+        v.cells, v.head1[0], v.head1[1], v.head1[2], v.head1[3], v.head0[0],
+        v.head0[1], v.head0[2], v.head0[3]);
+    local_eval += r & ~SCAN5_WALK_STOP;
+    if ((r & SCAN5_WALK_STOP) != 0) break;
   }
 
   block_add_evaluated(ctl, local_eval);

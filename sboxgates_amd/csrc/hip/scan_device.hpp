@@ -179,6 +179,11 @@ __device__ __forceinline__ u32 dev_uniform(u32 v) {
       __builtin_amdgcn_readfirstlane(static_cast<int>(v)));
 }
 
+__device__ __forceinline__ u64 dev_uniform64(u64 v) {
+  return static_cast<u64>(dev_uniform(static_cast<u32>(v))) |
+         static_cast<u64>(dev_uniform(static_cast<u32>(v >> 32))) << 32;
+}
+
 // Orders a wave's LDS writes before its later LDS reads in other lanes.
 // One wave's LDS operations complete in issue order, so this only has to
 // keep the compiler from moving them and make it wait for the writes.

@@ -25,10 +25,10 @@ constexpr int SCAN5_WIDE_MIN_ROW = 40;
 // 5-LUT scan: pools of at least this many gates run the wide kernel's
 // wave-owned variant (k_scan5_wave), which walks every triple on the
 // transposed pool and has no block barrier in its walk. Measured, full-range
-// scans: level with the batch kernel at 180 gates, 7 % less time at 220,
-// 17 % at 350 and 19 % at 450; more below (31 % at 120 gates, 53 % at 90), where
-// most triples have short rows and the per-triple set-up is all there is.
-constexpr int SCAN5_WAVE_MIN_POOL = 200;
+// scans: 3 % less time than the batch kernel at 150 gates, 43 % at 180, 52 %
+// at 220; more time below (11 % at 120 gates, 27 % at 90), where most
+// triples have one or two steps and the chunk set-up is most of the work.
+constexpr int SCAN5_WAVE_MIN_POOL = 150;
 // 32-gate words of the transposed pool per wide task (1 or 2).
 constexpr int SCAN5_WIDE_WORDS = 2;
 

@@ -7,9 +7,19 @@ engine functions it calls are gen_lut_ttable / tt_eq_mask, to re-evaluate a
 reported hit and to build the LUT tables of found7_naive, and
 function_lists, for the list the k=4 result indexes.
 
-Every mask used with it must hold at least one position where the target is
-1 (sparse_mask asserts it): that excludes the engine's "function 00 does not
-round-trip" special cases, so the oracle needs no knowledge of them.
+found5, found7 (and _oracle_shared.found4s) decide whether some circuit
+exists, so they take only masks that hold at least one position where the
+target is 1, and sparse_mask asserts that of every mask it makes: on such a
+mask the engine's "function 00 does not round-trip" rules (func == 0,
+fo == 0, fi forced identically 0 in sbg/lutcover.hpp) reject nothing that
+exists, and the oracle needs no knowledge of them. The suite as a whole is
+not restricted to such masks. onesided_masks makes the others: masks with
+only target-0 positions, only target-1 positions, or none. On those the
+reference is found3_onesided for k=3, whose verdict can be defined, and for
+the other kinds the CPU scan with the same seed, since whether a 5-LUT or
+shared-input candidate hits then depends on its random colouring
+(docs/PARITY.md); hits are re-evaluated and their function bytes checked by
+assert_hit_valid and assert_no_zero_function.
 """
 
 import collections
@@ -59,6 +69,33 @@ def sparse_mask(seed, size, target: bytes) -> bytes:
 
 def assert_mask_has_target1(target: bytes, mask: bytes):
     assert tt_int(target) & tt_int(mask), "mask holds no target-1 position"
+
+
+ONESIDED = ("Z1", "Z6", "Z40", "Zall", "O1", "O40", "Oall", "E")
+
+
+def onesided_masks(target: bytes, seed, num_inputs=8) -> dict:
+    """The one-sided masks of a target, by name: Z1, Z6, Z40 and Zall hold
+    1, 6, 40 sampled and all of the target-0 positions and no other; O1, O40
+    and Oall the same of the target-1 positions; E holds none. Positions are
+    those of a num_inputs-input function. Not made by sparse_mask, whose
+    assertion these masks exist to fail."""
+    t = tt_int(target)
+    size = 1 << num_inputs
+    zeros = [p for p in range(size) if not (t >> p) & 1]
+    ones = [p for p in range(size) if (t >> p) & 1]
+    rng = random.Random(seed)
+    picks = {"Z1": rng.sample(zeros, 1), "Z6": rng.sample(zeros, 6),
+             "Z40": rng.sample(zeros, min(40, len(zeros))), "Zall": zeros,
+             "O1": rng.sample(ones, 1),
+             "O40": rng.sample(ones, min(40, len(ones))), "Oall": ones,
+             "E": []}
+    out = {}
+    for name in ONESIDED:
+        m = sum(1 << p for p in picks[name])
+        assert not (m & t and m & ~t), name
+        out[name] = tt_bytes(m)
+    return out
 
 
 # --- combinations -----------------------------------------------------------
@@ -128,6 +165,18 @@ def cells(tabs, target, mask):
 def found3(tabs, target, mask):
     ones, zeros = cells(tabs, target, mask)
     return not (ones & zeros)
+
+
+def found3_onesided(tabs, target, mask):
+    """The 3-LUT verdict on any mask, one-sided ones included. The scan
+    never reports function byte 00, so it needs a function that is 1 on
+    some pattern: where no target-1 position is masked, that is a pattern
+    free of masked target-0 content, and a triple whose eight cells all hold
+    some is a miss although function 00 would fit."""
+    ones, zeros = cells(tabs, target, mask)
+    if ones:
+        return not (ones & zeros)
+    return len(zeros) < 8
 
 
 def feasible7(tabs, target, mask):
@@ -333,6 +382,16 @@ def hit_table(k, st, res, threes=None):
 
 def assert_hit_valid(k, st, res, target, mask, threes=None):
     assert tt_eq_mask(target, hit_table(k, st, res, threes), mask), (k, res)
+
+
+def assert_no_zero_function(k, res, threes=None):
+    """No function byte of a LUT hit is 00 (it does not round-trip through
+    the state); for k=4 the function the hit indexes."""
+    if k == 4:
+        assert threes[res[0]]["fun"] != 0, res
+    else:
+        count = {3: 1, 5: 2, 7: 3}[k]
+        assert all(0 < f < 256 for f in res[:count]), (k, res)
 
 
 # --- engines and the per-rank cases -----------------------------------------

@@ -1,7 +1,12 @@
 """The independent oracle of tests/_oracle.py against the CPU scans, on
 single-rank windows [r, r+1) for every rank of the per-rank cases that
 tests/test_gpu_per_rank.py runs on the GPU. Runs without a GPU, so the
-oracle is kept honest in the suite that runs everywhere."""
+oracle is kept honest in the suite that runs everywhere.
+
+Likewise the CPU references of tests/test_gpu_onesided_masks.py (the CPU
+scans on one-sided masks: hits valid, no zero function byte, the k=3 rule)
+and of tests/test_gpu_large_pools.py (the share of windows that hold a
+second hit, the rows that hit by their last rank)."""
 
 import itertools
 import math
@@ -10,6 +15,9 @@ import random
 import pytest
 
 import _oracle as orc
+import _oracle_large as lg
+import _oracle_onesided as one
+import test_gpu_sentinels as sen
 from conftest import rand_sparse_tt, rand_tt
 
 
@@ -202,6 +210,153 @@ def test_deep_hit_list_instance():
                                  seed=orc.SCAN_SEED)
     assert f_c and orc.hit_ids(7, r_c) == orc.DEEP7_COMB
     orc.assert_hit_valid(7, st, r_c, target, mask)
+
+
+# --- one-sided masks --------------------------------------------------------
+
+def test_onesided_masks_are_one_sided():
+    target = orc.cpu_engine(3).target(0)
+    t = orc.tt_int(target)
+    full = (1 << 256) - 1
+    masks = {n: orc.tt_int(m)
+             for n, m in orc.onesided_masks(target, one.MASK_SEED).items()}
+    assert list(masks) == list(orc.ONESIDED)
+    sizes = {n: bin(m).count("1") for n, m in masks.items()}
+    zeros = 256 - bin(t).count("1")
+    assert sizes == {"Z1": 1, "Z6": 6, "Z40": 40, "Zall": zeros, "O1": 1,
+                     "O40": 40, "Oall": 256 - zeros, "E": 0}
+    for name, m in masks.items():
+        assert not m & (t if name[0] == "Z" else ~t & full), name
+    # A 6-input target: positions below 64 only.
+    des = orc.tt_int(orc.tt_bytes(t & (1 << 64) - 1))
+    for m in orc.onesided_masks(orc.tt_bytes(des), 1, 6).values():
+        assert orc.tt_int(m) < 1 << 64
+
+
+@pytest.mark.parametrize("name", orc.ONESIDED)
+@pytest.mark.parametrize("kind", one.KINDS, ids=one.kind_id)
+def test_cpu_scans_on_onesided_masks(kind, name):
+    """What the GPU tests on one-sided masks take from the CPU scans: every
+    hit names its rank's combination, realises the target under the mask
+    and holds no zero function byte; cpu_scan3 follows found3_onesided on
+    every rank; and the masks that have to give both answers do."""
+    st, target, masks, total = one.setup(kind)
+    mask = masks[name]
+    ref = one.reference(kind, name)
+    assert len(ref) == total
+    tabs = [orc.tt_int(st.gate(i)["table"]) for i in range(st.num_gates)]
+    t, m = orc.tt_int(target), orc.tt_int(mask)
+    hits = 0
+    for r, (comb, f_c, r_c, ev_c) in enumerate(ref):
+        assert ev_c == 1, (r, comb)
+        if kind == 3:
+            assert f_c == orc.found3_onesided([tabs[i] for i in comb], t, m), \
+                (r, comb)
+        if f_c:
+            hits += 1
+            one.check_hit(kind, st, comb, r_c, target, mask)
+    print("%s %s: %d/%d hits" % (one.kind_id(kind), name, hits, total))
+    if kind in one.TWO_SIDED_KINDS and name in one.TWO_SIDED:
+        assert 0.02 <= hits / total <= 0.98, (hits, total)
+    if name in ("Z1", "Z6", "O1", "E") or kind == 7:
+        assert hits == total
+
+
+def test_onesided_ordered_windows_skip_misses():
+    """Zall and Z40 are the masks with something to order: a window behind
+    one of the first hits begins on a miss, so the lowest hit is not the
+    window's first rank."""
+    for kind in one.TWO_SIDED_KINDS:
+        for name in one.TWO_SIDED:
+            hits = one.hit_ranks(kind, name)
+            windows = one.ordered_windows(kind, name)
+            assert len(windows) == one.FIRST_HITS + 1
+            assert any(begin not in hits for begin, _ in windows), (kind, name)
+
+
+def test_found3_onesided_is_found3_on_two_sided_masks():
+    """The rule extends found3: on the sparse masks of the per-rank cases
+    the two agree on every rank."""
+    case = (3, 24, 6)
+    st, target, mask, _ = orc.case_setup(case)
+    tabs = [orc.tt_int(st.gate(i)["table"]) for i in range(case[1])]
+    t, m = orc.tt_int(target), orc.tt_int(mask)
+    for comb, verdict, _, _ in orc.case_reference(case):
+        g = [tabs[i] for i in comb]
+        assert orc.found3_onesided(g, t, m) == verdict == orc.found3(g, t, m)
+
+
+def test_scan5_verdict_on_zall_depends_on_the_seed():
+    """Why the CPU scan with the same seed, and no existence oracle, is the
+    reference on these masks: lut_solve_layers gives up on a split whose
+    random colouring forces fi to 0, so the verdict of some ranks changes
+    with the seed."""
+    st, target, masks, total = one.setup(5)
+    eng = orc.cpu_engine(3)
+    found = {seed: [bool(eng.scan_pool(5, st, target, masks["Zall"], r, r + 1,
+                                       seed=seed)[0]) for r in range(total)]
+             for seed in (7, 8)}
+    assert found[7] == [row[1] for row in one.reference(5, "Zall")]
+    differ = sum(a != b for a, b in zip(found[7], found[8]))
+    print("k=5 Zall: %d ranks differ between seeds 7 and 8" % differ)
+    assert differ >= 1
+
+
+# --- large pools ------------------------------------------------------------
+
+@pytest.mark.parametrize("case", lg.ORDERED_CASES, ids=lg.case_id)
+def test_large_pool_windows_hold_a_second_hit(case):
+    """The ordered-sentinel windows test the election only where a window
+    holds more than one hit: at least a third per (kind, pool). Every CPU
+    hit validates and lies at or below its sentinel."""
+    kind, n = case
+    st, _ = sen.pool(n)
+    ref = lg.ordered_reference(case)
+    for (comb, r, target, begin, end), (f_c, r_c, _) in zip(
+            lg.ordered_windows(case), ref):
+        assert f_c and begin <= r < end
+        lg.assert_hit_valid(kind, st, r_c, target)
+    multi, count = lg.multi_hit_windows(case)
+    print("%s: %d of %d windows hold a second hit"
+          % (lg.case_id(case), multi, count))
+    assert 3 * multi >= count
+
+
+@pytest.mark.parametrize("case", lg.ANYWHERE_CASES, ids=lg.case_id)
+def test_large_pool_rows_hit_by_their_last_rank(case):
+    """With gate n - 1's table as the target, the CPU scan of [b, b + n)
+    from a row's first rank hits at or before the row's last rank."""
+    kind, n = case
+    st, _ = sen.pool(n)
+    windows = lg.anywhere_windows(case)
+    assert len(windows) == 3 * lg.DRAWS
+    at_end = 0
+    for (b, row_end, end), (f_c, r_c, ev_c, rank, _) in zip(
+            windows, lg.anywhere_reference(case)):
+        assert f_c and b <= rank <= row_end < end, (b, rank, row_end)
+        assert ev_c == rank - b + 1
+        assert end - b <= n
+        lg.assert_hit_valid(kind, st, r_c, lg.anywhere_target(n))
+        at_end += rank == row_end
+    print("%s: %d of %d hits on the row's last rank"
+          % (lg.case_id(case), at_end, len(windows)))
+
+
+def test_large_pool_sentinel_lists():
+    for n in (200, 500):
+        total = math.comb(n, 7)
+        ranks = [orc.rank(c, n) for c in lg.sept_sentinels(n)]
+        assert total - 1 in ranks
+        assert total - math.comb(n - 1, 7) in ranks   # the first with a = 1
+    for n in (130, 450, 500):
+        combs = lg.shared_sentinels(n)
+        ranks = [orc.rank(c, n) for c in combs]
+        assert 0 in ranks and math.comb(n, 4) - 1 in ranks
+        for c in combs:
+            assert list(c) == sorted(set(c)) and 0 <= c[0] and c[3] < n
+        # First, a middle and last d of a row.
+        assert {(0, 1, 2, 3), (0, 1, 2, n - 1)} <= set(combs)
+        assert any(c[:3] == (0, 1, 2) and 3 < c[3] < n - 1 for c in combs)
 
 
 def test_window_case_has_unsolvable_runs():
